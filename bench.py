@@ -8,12 +8,15 @@ One "step" = one full `NOVAPipeline.__call__` (prompt embeddings -> point sets) 
 BASELINE.json's metric is quoted on: NOVA-d48w1024 (0.6B), 2048 points per sample, 64 AR steps x 25
 diffusion steps, CFG on, bf16, batch 32 PER GPU (weak scaling; configs[2] at N=1, configs[3] at
 N=8). Prompts are synthetic and already resident in HBM; weights are random-init (no network).
-Rank 0 prints ONE JSON line: whole-job generated points/s plus
-  roofline      the dominant kernel family (MFMA GEMM / attention), timed live with HIP events on the
-                launch stream inside the timed region (nova_prof_*), against the 2.5 PFLOP/s dense
-                bf16 MFMA peak of MI355X_MICROARCH.md
+Rank 0 prints ONE JSON line: whole-job generated points/s and ms_per_step. A plain run does nothing
+else: set up, warm up, time --steps steps, print. With --full the line also carries
+  roofline      the dominant kernel family (MFMA GEMM / attention), timed with HIP events on the
+                launch stream (nova_prof_*) in one extra serialised pass of the step after the timed
+                region, against the 2.5 PFLOP/s dense bf16 MFMA peak of MI355X_MICROARCH.md
   cpu_baseline  the oracle (oracle/nova_oracle.py, a port of the reference's CPU path) timed on the
                 host cores on a bounded sample of the same workload (rank 0, N=1 only).
+--dump-outputs DIR writes the point sets of the last timed step as DIR/points.npy (float32); with
+the same arguments every run draws the same weights, prompts and noise.
 """
 import argparse
 import json
@@ -170,6 +173,65 @@ def pmc_traffic(family, workload, fp8=False):
     return None, "no profiles/r*_pmc.json"
 
 
+def kernel_pass_fields(prof, prof_elapsed, dtype, workload):
+    """`roofline` and `kernels` of the --full line from the serialised kernel pass: per-slot (ms, work, launches) of the
+    library's HIP-event hooks and the wall time of the pass."""
+    BYTES = ("row_norm",)          # work counted in bytes (HBM-bound row kernels); the slots below carry no work figure
+    NOWORK = ("token_plumbing", "decoder_glue")
+    fams = {}
+    for k, (ms, wk, n) in prof.items():
+        if not n:
+            continue
+        fams[k] = {"ms": round(ms, 2), "launches": n}
+        if k not in NOWORK:
+            fams[k].update(rate=round(wk / ms / (1e6 if k in BYTES else 1e9), 2) if ms > 0 else 0.0, unit="GB/s" if k in BYTES else "TFLOP/s")
+    mfma = {k: v for k, v in fams.items() if k in MFMA_FAMILIES}
+
+    def peak_of(k):
+        # fp8 mode: the fc1 (+GELU), QKV (+RoPE) and fc2 kernels are pure fp8 launches -> dense fp8 peak; attention, the
+        # out-projection and the small-tile kernels are bf16
+        return MFMA_FP8_PEAK_TFLOPS if (dtype == "fp8" and k in ("gemm_bias_gelu", "qkv_gemm_rope", "gemm_bias_wide_k")) else MFMA_BF16_PEAK_TFLOPS
+
+    for k, v in mfma.items():
+        v["frac"] = round(v["rate"] / peak_of(k), 4)
+    pass_ms = prof_elapsed * 1e3
+    for v in fams.values():
+        v["share"] = round(v["ms"] / pass_ms, 4)
+    # the reported kernel: the family with the most time; families within 2 % of it count as tied and the tie goes to the
+    # LOWER fraction of peak (so the choice does not flip between runs towards the better-looking kernel)
+    top_ms = max(v["ms"] for v in mfma.values())
+    dom = min((k for k, v in mfma.items() if v["ms"] >= 0.98 * top_ms), key=lambda k: mfma[k]["frac"])
+    # HBM traffic of that kernel comes from a separate rocprofv3 --pmc run (counters cannot be read from inside the process);
+    # the committed summary is for one launch of that kernel at the workload's shapes, reported with its context.
+    traffic, traffic_note = pmc_traffic(dom, workload, fp8=dtype == "fp8")
+    peak = peak_of(dom)
+    work_tflop = {k: mfma[k]["rate"] * mfma[k]["ms"] / 1e3 for k in mfma}  # TFLOP executed per family in the pass
+    weighted = sum(work_tflop[k] / peak_of(k) for k in mfma) / (sum(v["ms"] for v in mfma.values()) / 1e3)
+    timed_ms = sum(v["ms"] for v in fams.values())
+    return {
+        "roofline": {"bound": "mfma", "kernel": dom, "achieved": mfma[dom]["rate"], "peak": peak,
+                     "unit": "TFLOP/s", "frac": round(mfma[dom]["rate"] / peak, 4), "traffic": traffic, "traffic_note": traffic_note,
+                     "clock_ghz_under_counters": pmc_traffic.clock_ghz,
+                     "clock_note": "shader clock the chip held under this kernel in the rocprofv3 counter passes (GRBM_GUI_ACTIVE / 8 / duration; "
+                                   "nominal 2.4 GHz, which `peak` is priced at); in-kernel clock reads of every encoder kernel, on random and on "
+                                   "zero-filled operands: profiles/r04_kernel_clock.txt (not measured in this run)",
+                     "avg_launch_ms": round(mfma[dom]["ms"] / mfma[dom]["launches"], 4),
+                     "share_of_step_time": mfma[dom]["share"],
+                     "kernel_choice": "family with the most time in the serialised pass; ties within 2 % go to the lower fraction",
+                     "families": {k: {"ms": v["ms"], "share": v["share"], "achieved": v["rate"], "frac": v["frac"]}
+                                  for k, v in sorted(mfma.items(), key=lambda kv: -kv[1]["ms"])},
+                     "mfma_time_weighted_frac": round(weighted, 4),
+                     "pass": {"ms": round(pass_ms, 1), "timed_kernels_ms": round(timed_ms, 1),
+                              "untimed_ms": round(pass_ms - timed_ms, 1),
+                              "note": "untimed = PyTorch's own kernels (draws, copies, argsort), launch gaps of the direct-launched "
+                                      "denoising loop and host time of the serialised pass; no library kernel is outside the slots"},
+                     "timing": "HIP events on the launch stream; one extra pass of the same step after the timed region with the "
+                               "two half-batch lanes serialised (concurrent lanes would put the other lane's kernels "
+                               "inside each event bracket)"},
+        "kernels": fams,
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -183,7 +245,10 @@ def main():
                     help="fp8: bf16 model with the encoder's QKV / fc1 / fc2 GEMMs on the block-scaled fp8 MFMA (configs[4]; never the headline)")
     ap.add_argument("--global-batch", type=int, default=0,
                     help="total samples over all ranks (0 = gpus x per-GPU batch); a value that does not divide gives ragged shards")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the serialised kernel pass (per-family timings, roofline) and the CPU baseline; off: the timed steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's point sets as DIR/points.npy (float32)")
     ap.add_argument("--cpu-dry-run", action="store_true",
                     help="rehearse the multi-process control flow on CPU (gloo, PyTorch module path, f32): not a measurement")
     args = ap.parse_args()
@@ -254,12 +319,17 @@ def main():
         pts = step()
     fence()
     elapsed = time.perf_counter() - t0
-    # Kernel pass (after the timed region, not part of `value`): the same step once more with the engine's two
+    if args.dump_outputs and rank == 0:
+        out = pts.cpu().numpy().astype(np.float32)
+        out = out[:max(1, (64 << 20) // out[0].nbytes)]  # leading samples up to 64 MB (a fixed sample of the batch)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "points.npy"), out)
+    # Kernel pass (--full; after the timed region, not part of `value`): the same step once more with the engine's two
     # half-batch lanes serialised and the library's HIP-event hooks on. In the timed region the lanes' kernels run
     # concurrently on two streams, so an event bracket around one kernel there also spans the other lane's kernels;
     # serialised, the brackets measure each kernel alone (and agree with rocprofv3 --kernel-trace, profiles/).
     prof, prof_elapsed = {}, 0.0
-    if not dry:
+    if args.full and not dry:
         hip.prof_enable(True)
         hip.prof_collect()
         t1 = time.perf_counter()
@@ -294,16 +364,6 @@ def main():
         fl = flops_per_sample(width, N, Nv, 256, schedule, args.diffusion_steps)
         value = G * N * args.steps / elapsed
         e2e_tflops = value / N * fl / 1e12 / world  # per GPU
-        BYTES = ("row_norm",)          # work counted in bytes (HBM-bound row kernels); the slots below carry no work figure
-        NOWORK = ("token_plumbing", "decoder_glue")
-        fams = {}
-        for k, (ms, wk, n) in prof.items():
-            if not n:
-                continue
-            fams[k] = {"ms": round(ms, 2), "launches": n}
-            if k not in NOWORK:
-                fams[k].update(rate=round(wk / ms / (1e6 if k in BYTES else 1e9), 2) if ms > 0 else 0.0, unit="GB/s" if k in BYTES else "TFLOP/s")
-        mfma = {k: v for k, v in fams.items() if k in MFMA_FAMILIES}
         if dry:
             # rehearsal only: rank 0 also generates the whole batch unsharded from the same seed - the gathered rows must
             # be the same samples in the same (prompt) order
@@ -319,27 +379,6 @@ def main():
                 dist.barrier()
                 dist.destroy_process_group()
             return
-        def peak_of(k):
-            # fp8 mode: the fc1 (+GELU), QKV (+RoPE) and fc2 kernels are pure fp8 launches -> dense fp8 peak; attention, the
-            # out-projection and the small-tile kernels are bf16
-            return MFMA_FP8_PEAK_TFLOPS if (args.dtype == "fp8" and k in ("gemm_bias_gelu", "qkv_gemm_rope", "gemm_bias_wide_k")) else MFMA_BF16_PEAK_TFLOPS
-
-        for k, v in mfma.items():
-            v["frac"] = round(v["rate"] / peak_of(k), 4)
-        pass_ms = prof_elapsed * 1e3
-        for v in fams.values():
-            v["share"] = round(v["ms"] / pass_ms, 4)
-        # the reported kernel: the family with the most time; families within 2 % of it count as tied and the tie goes to the
-        # LOWER fraction of peak (so the choice does not flip between runs towards the better-looking kernel)
-        top_ms = max(v["ms"] for v in mfma.values())
-        dom = min((k for k, v in mfma.items() if v["ms"] >= 0.98 * top_ms), key=lambda k: mfma[k]["frac"])
-        # HBM traffic of that kernel comes from a separate rocprofv3 --pmc run (counters cannot be read from inside the process);
-        # the committed summary is for one launch of that kernel at the workload's shapes, reported with its context.
-        traffic, traffic_note = pmc_traffic(dom, args.workload, fp8=args.dtype == "fp8")
-        peak = peak_of(dom)
-        work_tflop = {k: mfma[k]["rate"] * mfma[k]["ms"] / 1e3 for k in mfma}  # TFLOP executed per family in the pass
-        weighted = sum(work_tflop[k] / peak_of(k) for k in mfma) / (sum(v["ms"] for v in mfma.values()) / 1e3)
-        timed_ms = sum(v["ms"] for v in fams.values())
         rec = {
             "metric": "generated points/sec/node, NOVA-d48w1024 @2048 pts, 64-step sample" if args.workload.startswith("d48w1024")
             else f"generated points/sec/node, {args.workload}",
@@ -350,31 +389,13 @@ def main():
                        "diffusion_steps": args.diffusion_steps, "batch_per_gpu": B, "global_batch": G, "shards": shards,
                        "guidance": "cfg 2-pass", "sharding": f"batch rows over {world} GPU(s), all_gather of points",
                        "ranks_seen": ranks_seen, "process_group": (dist.get_backend() if distributed else "none")},
-            "roofline": {"bound": "mfma", "kernel": dom, "achieved": mfma[dom]["rate"], "peak": peak,
-                         "unit": "TFLOP/s", "frac": round(mfma[dom]["rate"] / peak, 4), "traffic": traffic, "traffic_note": traffic_note,
-                         "clock_ghz_under_counters": pmc_traffic.clock_ghz,
-                         "clock_note": "shader clock the chip held under this kernel in the rocprofv3 counter passes (GRBM_GUI_ACTIVE / 8 / duration; "
-                                       "nominal 2.4 GHz, which `peak` is priced at); in-kernel clock reads of every encoder kernel, on random and on "
-                                       "zero-filled operands: profiles/r04_kernel_clock.txt (not measured in this run)",
-                         "avg_launch_ms": round(mfma[dom]["ms"] / mfma[dom]["launches"], 4),
-                         "share_of_step_time": mfma[dom]["share"],
-                         "kernel_choice": "family with the most time in the serialised pass; ties within 2 % go to the lower fraction",
-                         "families": {k: {"ms": v["ms"], "share": v["share"], "achieved": v["rate"], "frac": v["frac"]}
-                                      for k, v in sorted(mfma.items(), key=lambda kv: -kv[1]["ms"])},
-                         "mfma_time_weighted_frac": round(weighted, 4),
-                         "pass": {"ms": round(pass_ms, 1), "timed_kernels_ms": round(timed_ms, 1),
-                                  "untimed_ms": round(pass_ms - timed_ms, 1),
-                                  "note": "untimed = PyTorch's own kernels (draws, copies, argsort), launch gaps of the direct-launched "
-                                          "denoising loop and host time of the serialised pass; no library kernel is outside the slots"},
-                         "timing": "HIP events on the launch stream; one extra pass of the same step after the timed region with the "
-                                   "two half-batch lanes serialised (concurrent lanes would put the other lane's kernels "
-                                   "inside each event bracket)"},
             "end_to_end": {"tflops_per_gpu": round(e2e_tflops, 1), "frac_of_mfma_peak": round(e2e_tflops / MFMA_BF16_PEAK_TFLOPS, 4),
                            "gflop_per_point": round(fl / N / 1e9, 2)},
-            "kernels": fams,
         }
-        if world == 1 and not args.no_cpu_baseline:
-            rec["cpu_baseline"] = cpu_baseline(pipe, width, heads, H, W, threads=host_cores(), with_config0=args.workload.startswith("d48w1024"))
+        if args.full:
+            rec.update(kernel_pass_fields(prof, prof_elapsed, args.dtype, args.workload))
+            if world == 1 and not args.no_cpu_baseline:
+                rec["cpu_baseline"] = cpu_baseline(pipe, width, heads, H, W, threads=host_cores(), with_config0=args.workload.startswith("d48w1024"))
         print(json.dumps(rec), flush=True)
     if distributed:
         dist.barrier()

@@ -31,3 +31,22 @@ def test_workloads_name_the_baseline_configs():
 
 def test_host_cores_is_bounded():
     assert 1 <= bench.host_cores() <= 32
+
+
+def test_dump_outputs_write_the_last_step_points_the_same_every_run(tmp_path):
+    """--dump-outputs DIR: the point sets of the last timed step as DIR/points.npy in float32, identical from run to run with the
+    same arguments (the control flow rehearsed on CPU at a toy size)."""
+    import subprocess
+
+    import numpy as np
+
+    got = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--cpu-dry-run",
+               "--workload", "d48w768_256pts_b1", "--ar-steps", "2", "--diffusion-steps", "2", "--global-batch", "2",
+               "--dump-outputs", str(tmp_path / run)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        got.append(np.load(tmp_path / run / "points.npy"))
+    assert got[0].shape == (2, 256, 3) and got[0].dtype == np.float32 and np.isfinite(got[0]).all()
+    assert np.array_equal(got[0], got[1])

@@ -212,7 +212,7 @@ def test_bench_launch_contract_one_rank_on_rccl(hip):
     """The driver's N > 1 launch line (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
     127.0.0.1 --master-port P bench.py --gpus N ...`) with N = 1 on this box's GPU: RCCL process group, barrier-bracketed
     timing, all_gather of the generated point sets, max-over-ranks time, ONE JSON line from rank 0 (reduced AR / diffusion
-    step counts; the contract, not the number, is under test)."""
+    step counts; the contract, not the number, is under test). `--full`: the roofline of the serialised kernel pass is checked too."""
     import json
     import subprocess
 
@@ -220,7 +220,7 @@ def test_bench_launch_contract_one_rank_on_rccl(hip):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", "29641", os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1",
-           "--workload", "d48w768_1024pts_b8", "--ar-steps", "6", "--diffusion-steps", "3", "--no-cpu-baseline"]
+           "--workload", "d48w768_1024pts_b8", "--ar-steps", "6", "--diffusion-steps", "3", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
