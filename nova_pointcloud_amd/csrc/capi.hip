@@ -458,6 +458,15 @@ int nova_pointset_pairwise_dist(const float* x, const float* y, float* D, int B,
   return pointset_pairwise_dist(x, y, D, B, N, M, clamp_lo, clamp_hi, (hipStream_t)stream);
 }
 
+int nova_pointset_chamfer_matrix(const float* x, const float* y, float* cd, int A, int B, int N, int M, int ldc, int symmetric,
+                                 void* stream) {
+  NOVA_REQUIRE(A <= 0 || B <= 0 || (x && y && cd), NOVA_ERR_ARG, "pointset_chamfer_matrix: null pointer");
+  NOVA_REQUIRE(ldc >= B, NOVA_ERR_ARG, "pointset_chamfer_matrix: ldc %d < B %d", ldc, B);
+  NOVA_REQUIRE(!symmetric || (x == y && A == B && N == M), NOVA_ERR_ARG,
+               "pointset_chamfer_matrix: symmetric mode needs x == y, A == B and N == M");
+  return pointset_chamfer_matrix(x, y, cd, A, B, N, M, ldc, symmetric, (hipStream_t)stream);
+}
+
 int nova_modulate_rows(const void* x, const void* mod, void* out, long rows, int D, int dtype, void* stream) {
   NOVA_REQUIRE(!bad_dtype(dtype), NOVA_ERR_ARG, "modulate_rows: bad dtype %d", dtype);
   NOVA_REQUIRE(rows == 0 || (x && mod && out), NOVA_ERR_ARG, "modulate_rows: null pointer");

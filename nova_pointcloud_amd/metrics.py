@@ -8,9 +8,15 @@ Same function names, arguments and results as the reference's evaluation code
 with the O(N M) distance work (torch.cdist + min, the assignment cost matrix) in libnova_hip.so
 (csrc/pointset.hip). The optimal assignment itself is scipy's linear_sum_assignment on the host, exactly as in the
 reference. GPU tensors only: there is no CPU path here (NovaHipError for CPU tensors or a missing library).
+
+Set-level quality of a generated set against a reference set (MMD, COV, 1-NNA under the Chamfer distance, the numbers
+of PointFlow and its successors): chamfer_matrix (csrc/chamfer.hip), distribution_metrics_from_matrices,
+compute_all_metrics, and load_point_clouds for what save_point_clouds or `bench.py --dump-outputs` wrote.
 """
 import json
+import math
 import os
+import re
 
 import numpy as np
 import torch
@@ -109,6 +115,121 @@ def robust_emd(pred, gt):
 
 
 # ----------------------------------------------------------------------------------------------------
+# set-level metrics: MMD, COV and 1-NNA under the Chamfer distance
+# ----------------------------------------------------------------------------------------------------
+METRIC_KEYS = ("lgan_mmd-CD", "lgan_mmd_smp-CD", "lgan_cov-CD", "1-NN-CD-acc", "1-NN-CD-acc_t", "1-NN-CD-acc_f")
+_DISTANCES_PER_LAUNCH = 1 << 37  # ~1.4e11 squared distances: tens of milliseconds per launch (profiles/chamfer_matrix_*)
+
+
+def _finite_points(*named):
+    """_points for each (tensor, name), after checking every tensor's shape and finiteness (ValueError) first."""
+    for t, name in named:
+        if torch.is_tensor(t):
+            if t.dim() != 3 or t.shape[-1] != 3:
+                raise ValueError(f"{name}: expected [S, n, 3] clouds, got {tuple(t.shape)}")
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError(f"{name}: points must be finite")
+    return [_points(t, name) for t, name in named]
+
+
+def chamfer_matrix(x, y=None, max_pairs_per_launch=None):
+    """cd[a, b] = CD(x[a], y[b]) for clouds x [A, N, 3] and y [B, M, 3] on the GPU: float32 [A, B] on x's device, with
+
+        CD(X, Y) = mean_{p in X} min_{q in Y} |p - q|^2 + mean_{q in Y} min_{p in X} |p - q|^2
+
+    in squared Euclidean distances, no clamp and no normalisation (the convention of PointFlow and its successors; not
+    the density-weighted compute_chamfer_distance). y=None is x against itself: only the pairs a <= b are computed and
+    the result is exactly symmetric. The pair grid is split into launches of at most `max_pairs_per_launch` cloud pairs
+    (default: ~1.4e11 squared distances each); every entry is bitwise the same whatever the split."""
+    sym = y is None
+    x, y = _finite_points((x, "x")) * 2 if sym else _finite_points((x, "x"), (y, "y"))
+    if y.device != x.device:
+        raise ValueError(f"x is on {x.device}, y on {y.device}")
+    A, N, B, M = x.shape[0], x.shape[1], y.shape[0], y.shape[1]
+    cd = torch.empty(A, B, dtype=torch.float32, device=x.device)
+    if A == 0 or B == 0:
+        return cd
+    if N == 0 or M == 0:
+        raise ValueError(f"chamfer_matrix: empty clouds ({N} and {M} points)")
+    pairs = max_pairs_per_launch if max_pairs_per_launch is not None else max(1, _DISTANCES_PER_LAUNCH // (N * M))
+    if pairs < 1:
+        raise ValueError(f"max_pairs_per_launch must be >= 1, got {pairs}")
+    bs = max(1, math.isqrt(pairs))  # square blocks; a diagonal block holds bs (bs + 1) / 2 <= pairs pairs
+    with torch.cuda.device(x.device):
+        st = hip.stream_ptr()
+
+        def launch(a0, a1, b0, b1, symmetric):
+            hip.call("nova_pointset_chamfer_matrix", x[a0].data_ptr(), y[b0].data_ptr(), cd[a0, b0:].data_ptr(), a1 - a0, b1 - b0,
+                     N, M, B, 1 if symmetric else 0, st)
+
+        if sym:
+            for a0 in range(0, A, bs):
+                a1 = min(A, a0 + bs)
+                launch(a0, a1, a0, a1, True)
+                for b0 in range(a1, A, bs):
+                    b1 = min(A, b0 + bs)
+                    launch(a0, a1, b0, b1, False)
+                    cd[b0:b1, a0:a1] = cd[a0:a1, b0:b1].t()
+        else:
+            bb = min(B, max(bs, pairs // min(A, bs)))  # wide blocks when A is short
+            ba = min(A, max(1, pairs // bb))
+            for a0 in range(0, A, ba):
+                for b0 in range(0, B, bb):
+                    launch(a0, min(A, a0 + ba), b0, min(B, b0 + bb), False)
+    return cd
+
+
+def _first_argmin(d, dim):
+    """Index of the minimum along `dim`, ties to the lowest index (spelled out rather than relying on a backend)."""
+    m = d.min(dim=dim, keepdim=True).values
+    idx = torch.arange(d.shape[dim], device=d.device).view([-1 if k == dim else 1 for k in range(d.dim())])
+    return torch.where(d == m, idx, d.shape[dim]).min(dim=dim).values
+
+
+def distribution_metrics_from_matrices(d_rs, d_rr, d_ss):
+    """The six set-level metrics from the Chamfer matrices of a reference set R (S_r clouds) and a sample set Sm (S_s):
+    d_rs [S_r, S_s] = CD(R_r, Sm_s), d_rr [S_r, S_r], d_ss [S_s, S_s]. Pure tensor logic (CPU or GPU); 0-dim float64
+    tensors on d_rs's device, keyed as PointFlow's evaluation code keys them:
+
+        lgan_mmd-CD      mean_r min_s d_rs[r, s]
+        lgan_mmd_smp-CD  mean_s min_r d_rs[r, s]
+        lgan_cov-CD      |{argmin_r d_rs[r, s] : s}| / S_r            (argmin ties to the lowest r)
+        1-NN-CD-acc      1-NN classifier accuracy on the pooled set [R; Sm] with the matrix [[d_rr, d_rs], [d_rs^T, d_ss]]:
+                         each element's nearest other element (diagonal excluded, ties to the lowest pooled index) is
+                         correct when it carries the same label; the fraction over all elements
+        1-NN-CD-acc_t    the same fraction over the references only
+        1-NN-CD-acc_f    the same fraction over the samples only"""
+    S_r, S_s = d_rs.shape
+    if tuple(d_rr.shape) != (S_r, S_r) or tuple(d_ss.shape) != (S_s, S_s) or S_r == 0 or S_s == 0:
+        raise ValueError(f"matrix shapes {tuple(d_rs.shape)}, {tuple(d_rr.shape)}, {tuple(d_ss.shape)} do not form a pooled matrix")
+    d_rs, d_rr, d_ss = d_rs.double(), d_rr.to(d_rs.device).double(), d_ss.to(d_rs.device).double()
+    out = {"lgan_mmd-CD": d_rs.min(dim=1).values.mean(), "lgan_mmd_smp-CD": d_rs.min(dim=0).values.mean()}
+    # the fractions are integer counts divided once in float64 on the host (a device mean may multiply by 1 / n)
+    frac = lambda count, total: torch.tensor(int(count) / total, dtype=torch.float64, device=d_rs.device)
+    out["lgan_cov-CD"] = frac(torch.unique(_first_argmin(d_rs, 0)).numel(), S_r)
+    pooled = torch.cat([torch.cat([d_rr, d_rs], 1), torch.cat([d_rs.t(), d_ss], 1)], 0)
+    pooled.fill_diagonal_(float("inf"))
+    is_ref = torch.arange(S_r + S_s, device=d_rs.device) < S_r
+    correct = is_ref[_first_argmin(pooled, 1)] == is_ref
+    n_t, n_f = int(correct[:S_r].sum()), int(correct[S_r:].sum())
+    out["1-NN-CD-acc"], out["1-NN-CD-acc_t"], out["1-NN-CD-acc_f"] = frac(n_t + n_f, S_r + S_s), frac(n_t, S_r), frac(n_f, S_s)
+    return out
+
+
+def compute_all_metrics(sample_pcs, ref_pcs, batch_size=None):
+    """MMD, COV and 1-NNA under the Chamfer distance (see distribution_metrics_from_matrices) of the generated clouds
+    sample_pcs [S_s, N, 3] against the reference clouds ref_pcs [S_r, M, 3], both GPU tensors. `batch_size` caps the
+    cloud pairs per kernel launch (chamfer_matrix's max_pairs_per_launch). Returns a dict of Python floats."""
+    smp, ref = _finite_points((sample_pcs, "sample_pcs"), (ref_pcs, "ref_pcs"))
+    if smp.shape[0] == 0 or ref.shape[0] == 0:
+        raise ValueError("compute_all_metrics: empty set")
+    d_rs = chamfer_matrix(ref, smp, batch_size)
+    d_rr = chamfer_matrix(ref, None, batch_size)
+    d_ss = chamfer_matrix(smp, None, batch_size)
+    return {k: float(v) for k, v in distribution_metrics_from_matrices(d_rs, d_rr, d_ss).items()}
+
+
+# ----------------------------------------------------------------------------------------------------
 # normalisation and export
 # ----------------------------------------------------------------------------------------------------
 class GlobalNormalizer(object):
@@ -147,3 +268,29 @@ def save_point_clouds(points, prefix, directory="."):
         paths.append(os.path.join(directory, f"{prefix}_{i}.npy"))
         np.save(paths[-1], pc)
     return paths
+
+
+def _natural_key(name):
+    return [int(t) if t.isdigit() else t for t in re.split(r"(\d+)", name)]
+
+
+def load_point_clouds(path):
+    """A point set as float32 numpy [S, n, 3] from either a `.npy` file holding [S, n, 3] (what `bench.py --dump-outputs
+    DIR` writes as DIR/points.npy) or a directory of per-cloud [n, 3] `.npy` files (what save_point_clouds writes; read
+    in natural name order, so `x_2.npy` comes before `x_10.npy`). Raises FileNotFoundError or ValueError."""
+    if os.path.isdir(path):
+        names = sorted((f for f in os.listdir(path) if f.endswith(".npy")), key=_natural_key)
+        if not names:
+            raise FileNotFoundError(f"{path}: no .npy files")
+        clouds = [np.load(os.path.join(path, f), allow_pickle=False) for f in names]
+        for f, c in zip(names, clouds):
+            if c.ndim != 2 or c.shape[-1] != 3 or c.shape != clouds[0].shape:
+                raise ValueError(f"{os.path.join(path, f)}: expected [{clouds[0].shape[0]}, 3] points like the first file, got {c.shape}")
+        pts = np.stack(clouds)
+    elif os.path.isfile(path):
+        pts = np.load(path, allow_pickle=False)
+        if pts.ndim != 3 or pts.shape[-1] != 3:
+            raise ValueError(f"{path}: expected [S, n, 3] points, got {pts.shape}")
+    else:
+        raise FileNotFoundError(path)
+    return np.ascontiguousarray(pts, dtype=np.float32)

@@ -1,0 +1,51 @@
+"""Set-level quality of generated point clouds against a reference set: MMD, COV and 1-NNA under the Chamfer distance.
+
+    python scripts/eval_pointsets.py SAMPLES REFS [--out FILE]
+
+SAMPLES and REFS are each a `.npy` holding [S, n, 3] (what `bench.py --dump-outputs DIR` writes as DIR/points.npy) or a
+directory of per-cloud [n, 3] `.npy` files (what metrics.save_point_clouds writes). Points are used as given: normalise
+both sets the same way first (e.g. metrics.GlobalNormalizer). Prints one JSON line with the six metrics
+(metrics.distribution_metrics_from_matrices), the set sizes and the seconds taken; --out writes the same line to FILE.
+Runs on the GPU only (the all-pairs Chamfer matrices are HIP kernels) and fails without one.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from nova_pointcloud_amd import hip, metrics  # noqa: E402
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("samples", help="generated clouds: [S, n, 3] .npy or a directory of [n, 3] .npy files")
+    ap.add_argument("refs", help="reference clouds: [S, n, 3] .npy or a directory of [n, 3] .npy files")
+    ap.add_argument("--out", help="also write the JSON line to this file")
+    ap.add_argument("--batch-size", type=int, default=None, help="cloud pairs per kernel launch (default: the library's cap)")
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise hip.NovaHipError("eval_pointsets.py needs an MI355X GPU: the Chamfer matrices have no CPU path")
+    smp = torch.from_numpy(metrics.load_point_clouds(args.samples)).cuda()
+    ref = torch.from_numpy(metrics.load_point_clouds(args.refs)).cuda()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = metrics.compute_all_metrics(smp, ref, batch_size=args.batch_size)
+    res.update({"n_samples": smp.shape[0], "n_refs": ref.shape[0], "sample_points": smp.shape[1], "ref_points": ref.shape[1],
+                "seconds": round(time.perf_counter() - t0, 4)})
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    return res
+
+
+if __name__ == "__main__":
+    main()
