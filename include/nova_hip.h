@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NOVA_HIP_VERSION 402 /* 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
+#define NOVA_HIP_VERSION 403 /* 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
 
 typedef enum { NOVA_F32 = 0, NOVA_BF16 = 1, NOVA_F16 = 2 } nova_dtype;
 typedef enum { NOVA_ACT_NONE = 0, NOVA_ACT_GELU_ERF = 1, NOVA_ACT_SILU = 2 } nova_act;
@@ -256,6 +256,29 @@ int nova_pointset_pairwise_dist(const float* x, const float* y, float* D, int B,
  * an entry does not depend on how the caller splits the pair grid. Coordinates must be finite and of magnitude << 1e18. */
 int nova_pointset_chamfer_matrix(const float* x, const float* y, float* cd, int A, int B, int N, int M, int ldc, int symmetric,
                                  void* stream);
+/* emd[a * ldc + b] = EMD(x[a], y[b]) for x [A, N, 3] and y [B, N, 3] float32 clouds of the same point count,
+ * 1 <= N <= NOVA_EMD_MAX_POINTS: the EMD of the set-level metrics (MMD, COV, 1-NNA) of the point-cloud generation
+ * literature, which is not the exact assignment but the approximate matching of Fan et al. ("approxmatch") followed by
+ * its match cost, divided by n (PointFlow's emd_approx). For X = {p_k}, Y = {q_l} and d2[k, l] = |p_k - q_l|^2
+ * (squared Euclidean, float32 input used as given, no clamp and no normalisation):
+ *   remainL[k] = 1, remainR[l] = 1, cost = 0
+ *   for j in 7, 6, 5, 4, 3, 2, 1, 0, -1, -2:                  # 10 levels
+ *       level = -(4 ** j)            (j = -2: level = 0)       # -16384, -4096, ..., -0.25, 0
+ *       E[k, l] = exp(level * d2[k, l])
+ *       A (per k):  ratioL[k] = remainL[k] / (1e-9 + sum_l E[k, l] * remainR[l])
+ *       B (per l):  s = remainR[l] * sum_k E[k, l] * ratioL[k]
+ *                   ratioR[l] = min(remainR[l] / (s + 1e-9), 1) * remainR[l]
+ *                   remainR[l] = max(0, remainR[l] - s)
+ *       C (per k):  w[k, l] = E[k, l] * ratioL[k] * ratioR[l]
+ *                   cost += sum_l w[k, l] * sqrt(d2[k, l]);   remainL[k] = max(0, remainL[k] - sum_l w[k, l])
+ *   EMD(X, Y) = cost / n
+ * It is NOT symmetric: EMD(X, Y) != EMD(Y, X) in general (x, the first cloud, carries remainL). It is
+ * translation-invariant but not scale-invariant (the levels are absolute squared distances), so normalise the points
+ * the way the compared work does. All mass is moved, so it is >= the exact-assignment EMD. One workgroup writes each
+ * entry and every sum runs in a fixed order: an entry does not depend on how the caller splits the pair grid.
+ * NOVA_ERR_ARG for null pointers (A, B > 0), ldc < B, N < 1 or N > NOVA_EMD_MAX_POINTS. Coordinates must be finite. */
+#define NOVA_EMD_MAX_POINTS 4096
+int nova_pointset_emd_matrix(const float* x, const float* y, float* emd, int A, int B, int N, int ldc, void* stream);
 
 /* ---- composite entry points (what the AR loop actually calls) --------------------------------
  * One ViT block's parameters (reference state_dict names in comments). GEMM weights in `dtype`,

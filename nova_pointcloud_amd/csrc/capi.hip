@@ -467,6 +467,14 @@ int nova_pointset_chamfer_matrix(const float* x, const float* y, float* cd, int 
   return pointset_chamfer_matrix(x, y, cd, A, B, N, M, ldc, symmetric, (hipStream_t)stream);
 }
 
+int nova_pointset_emd_matrix(const float* x, const float* y, float* emd, int A, int B, int N, int ldc, void* stream) {
+  NOVA_REQUIRE(A <= 0 || B <= 0 || (x && y && emd), NOVA_ERR_ARG, "pointset_emd_matrix: null pointer");
+  NOVA_REQUIRE(ldc >= B, NOVA_ERR_ARG, "pointset_emd_matrix: ldc %d < B %d", ldc, B);
+  NOVA_REQUIRE(N >= 1 && N <= NOVA_EMD_MAX_POINTS, NOVA_ERR_ARG,
+               "pointset_emd_matrix: N %d outside 1 .. %d (the maximum point count NOVA_EMD_MAX_POINTS)", N, NOVA_EMD_MAX_POINTS);
+  return pointset_emd_matrix(x, y, emd, A, B, N, ldc, (hipStream_t)stream);
+}
+
 int nova_modulate_rows(const void* x, const void* mod, void* out, long rows, int D, int dtype, void* stream) {
   NOVA_REQUIRE(!bad_dtype(dtype), NOVA_ERR_ARG, "modulate_rows: bad dtype %d", dtype);
   NOVA_REQUIRE(rows == 0 || (x && mod && out), NOVA_ERR_ARG, "modulate_rows: null pointer");

@@ -148,5 +148,7 @@ int pointset_pairwise_dist(const float* x, const float* y, float* D, int B, int 
 // ---- chamfer.hip (all-pairs Chamfer matrix for MMD / COV / 1-NNA)
 int pointset_chamfer_matrix(const float* x, const float* y, float* cd, int A, int B, int N, int M, int ldc, int symmetric,
                             hipStream_t st);
+// ---- emd.hip (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA; point counts 1 .. EMD_MAX_N)
+int pointset_emd_matrix(const float* x, const float* y, float* emd, int A, int B, int N, int ldc, hipStream_t st);
 
 }  // namespace nova

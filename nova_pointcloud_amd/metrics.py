@@ -11,7 +11,10 @@ reference. GPU tensors only: there is no CPU path here (NovaHipError for CPU ten
 
 Set-level quality of a generated set against a reference set (MMD, COV, 1-NNA under the Chamfer distance, the numbers
 of PointFlow and its successors): chamfer_matrix (csrc/chamfer.hip), distribution_metrics_from_matrices,
-compute_all_metrics, and load_point_clouds for what save_point_clouds or `bench.py --dump-outputs` wrote.
+compute_all_metrics, and load_point_clouds for what save_point_clouds or `bench.py --dump-outputs` wrote. The same three
+metrics under the EMD of that literature (compute_all_metrics(..., emd=True)) run on emd_matrix (csrc/emd.hip): the
+approximate matching of Fan et al. ("approxmatch", PointFlow's emd_approx), not the exact assignment of
+compute_emd_distance above. It is asymmetric, so the full matrices are computed and oriented as PointFlow orients them.
 """
 import json
 import math
@@ -119,6 +122,9 @@ def robust_emd(pred, gt):
 # ----------------------------------------------------------------------------------------------------
 METRIC_KEYS = ("lgan_mmd-CD", "lgan_mmd_smp-CD", "lgan_cov-CD", "1-NN-CD-acc", "1-NN-CD-acc_t", "1-NN-CD-acc_f")
 _DISTANCES_PER_LAUNCH = 1 << 37  # ~1.4e11 squared distances: tens of milliseconds per launch (profiles/chamfer_matrix_*)
+EMD_METRIC_KEYS = ("lgan_mmd-EMD", "lgan_mmd_smp-EMD", "lgan_cov-EMD", "1-NN-EMD-acc", "1-NN-EMD-acc_t", "1-NN-EMD-acc_f")
+EMD_MAX_POINTS = 4096  # == NOVA_EMD_MAX_POINTS of include/nova_hip.h
+_EMD_EVALUATIONS_PER_LAUNCH = 1 << 36  # (k, l, level) evaluations, ~6.9e10: tens of milliseconds per launch (profiles/emd_matrix_*)
 
 
 def _finite_points(*named):
@@ -179,6 +185,64 @@ def chamfer_matrix(x, y=None, max_pairs_per_launch=None):
     return cd
 
 
+def _emd_resident_workgroups(device, N):
+    """Workgroups of emd_matrix_kernel resident at once on the device: CUs x what LDS allows per CU (csrc/emd.hip keeps
+    36 B per point of capacity - 256, 512, 1024, 2048 or 4096 points - in LDS; the registers allow the same or more)."""
+    capacity = next(c for c in (256, 512, 1024, 2048, 4096) if N <= c)
+    waves = 8 if capacity == 4096 else 4
+    per_cu = max(1, min((160 * 1024) // (36 * capacity + 64), 32 // waves))
+    return torch.cuda.get_device_properties(device).multi_processor_count * per_cu
+
+
+def _emd_point_counts(named):
+    """ValueError unless the [S, n, 3] tensors of `named` share one point count n in 1 .. EMD_MAX_POINTS (checked before
+    _finite_points, so it holds for CPU tensors too)."""
+    counts = {t.shape[1] for t, _ in named if torch.is_tensor(t) and t.dim() == 3}
+    if len(counts) > 1:
+        raise ValueError(f"the EMD needs equal point counts (got {' and '.join(f'{t.shape[1]} ({n})' for t, n in named)})")
+    if counts and not 1 <= min(counts) <= EMD_MAX_POINTS:
+        raise ValueError(f"the EMD kernel takes 1 .. {EMD_MAX_POINTS} points per cloud, got {min(counts)}")
+
+
+def emd_matrix(x, y=None, max_pairs_per_launch=None):
+    """emd[a, b] = EMD(x[a], y[b]) for clouds x [A, N, 3] and y [B, N, 3] on the GPU: float32 [A, B] on x's device. The
+    EMD is approxmatch followed by its match cost, divided by n (PointFlow's emd_approx; the algorithm is spelled out
+    in include/nova_hip.h at nova_pointset_emd_matrix), on squared Euclidean distances with no clamp and no
+    normalisation. It is NOT symmetric: x[a] is the first cloud. It is translation-invariant but not scale-invariant, so
+    normalise the points the way the compared work does. Both sets need the same point count N, 1 <= N <= 4096.
+
+    y=None is x against itself: the full matrix is computed (not mirrored). The pair grid is split into launches of at
+    most `max_pairs_per_launch` cloud pairs (default: ~6.9e10 (k, l, level) evaluations each, in whole rounds of the
+    resident workgroups); every entry is bitwise the same whatever the split."""
+    _emd_point_counts([(x, "x")] if y is None else [(x, "x"), (y, "y")])
+    x, y = _finite_points((x, "x")) * 2 if y is None else _finite_points((x, "x"), (y, "y"))
+    if y.device != x.device:
+        raise ValueError(f"x is on {x.device}, y on {y.device}")
+    A, N, B = x.shape[0], x.shape[1], y.shape[0]
+    emd = torch.empty(A, B, dtype=torch.float32, device=x.device)
+    if A == 0 or B == 0:
+        return emd
+    if max_pairs_per_launch is None:
+        res = _emd_resident_workgroups(x.device, N)
+        pairs = max(1, _EMD_EVALUATIONS_PER_LAUNCH // (N * N * 10) // res) * res
+    else:
+        pairs = max_pairs_per_launch
+        if pairs < 1:
+            raise ValueError(f"max_pairs_per_launch must be >= 1, got {pairs}")
+        res = pairs
+    bb = min(B, res, pairs)  # column blocks of a round's width; rows fill the launch
+    with torch.cuda.device(x.device):
+        st = hip.stream_ptr()
+        for b0 in range(0, B, bb):
+            b1 = min(B, b0 + bb)
+            ba = max(1, pairs // (b1 - b0))
+            for a0 in range(0, A, ba):
+                a1 = min(A, a0 + ba)
+                hip.call("nova_pointset_emd_matrix", x[a0].data_ptr(), y[b0].data_ptr(), emd[a0, b0:].data_ptr(), a1 - a0,
+                         b1 - b0, N, B, st)
+    return emd
+
+
 def _first_argmin(d, dim):
     """Index of the minimum along `dim`, ties to the lowest index (spelled out rather than relying on a backend)."""
     m = d.min(dim=dim, keepdim=True).values
@@ -186,7 +250,7 @@ def _first_argmin(d, dim):
     return torch.where(d == m, idx, d.shape[dim]).min(dim=dim).values
 
 
-def distribution_metrics_from_matrices(d_rs, d_rr, d_ss):
+def distribution_metrics_from_matrices(d_rs, d_rr, d_ss, distance="CD"):
     """The six set-level metrics from the Chamfer matrices of a reference set R (S_r clouds) and a sample set Sm (S_s):
     d_rs [S_r, S_s] = CD(R_r, Sm_s), d_rr [S_r, S_r], d_ss [S_s, S_s]. Pure tensor logic (CPU or GPU); 0-dim float64
     tensors on d_rs's device, keyed as PointFlow's evaluation code keys them:
@@ -198,35 +262,54 @@ def distribution_metrics_from_matrices(d_rs, d_rr, d_ss):
                          each element's nearest other element (diagonal excluded, ties to the lowest pooled index) is
                          correct when it carries the same label; the fraction over all elements
         1-NN-CD-acc_t    the same fraction over the references only
-        1-NN-CD-acc_f    the same fraction over the samples only"""
+        1-NN-CD-acc_f    the same fraction over the samples only
+
+    `distance` sets only the key suffix ("CD" or "EMD"). For an asymmetric distance pass the matrices oriented as the
+    row rule above needs them (compute_all_metrics(..., emd=True) shows how)."""
+    if distance not in ("CD", "EMD"):
+        raise ValueError(f"distance must be 'CD' or 'EMD', got {distance!r}")
     S_r, S_s = d_rs.shape
     if tuple(d_rr.shape) != (S_r, S_r) or tuple(d_ss.shape) != (S_s, S_s) or S_r == 0 or S_s == 0:
         raise ValueError(f"matrix shapes {tuple(d_rs.shape)}, {tuple(d_rr.shape)}, {tuple(d_ss.shape)} do not form a pooled matrix")
     d_rs, d_rr, d_ss = d_rs.double(), d_rr.to(d_rs.device).double(), d_ss.to(d_rs.device).double()
-    out = {"lgan_mmd-CD": d_rs.min(dim=1).values.mean(), "lgan_mmd_smp-CD": d_rs.min(dim=0).values.mean()}
+    out = {f"lgan_mmd-{distance}": d_rs.min(dim=1).values.mean(), f"lgan_mmd_smp-{distance}": d_rs.min(dim=0).values.mean()}
     # the fractions are integer counts divided once in float64 on the host (a device mean may multiply by 1 / n)
     frac = lambda count, total: torch.tensor(int(count) / total, dtype=torch.float64, device=d_rs.device)
-    out["lgan_cov-CD"] = frac(torch.unique(_first_argmin(d_rs, 0)).numel(), S_r)
+    out[f"lgan_cov-{distance}"] = frac(torch.unique(_first_argmin(d_rs, 0)).numel(), S_r)
     pooled = torch.cat([torch.cat([d_rr, d_rs], 1), torch.cat([d_rs.t(), d_ss], 1)], 0)
     pooled.fill_diagonal_(float("inf"))
     is_ref = torch.arange(S_r + S_s, device=d_rs.device) < S_r
     correct = is_ref[_first_argmin(pooled, 1)] == is_ref
     n_t, n_f = int(correct[:S_r].sum()), int(correct[S_r:].sum())
-    out["1-NN-CD-acc"], out["1-NN-CD-acc_t"], out["1-NN-CD-acc_f"] = frac(n_t + n_f, S_r + S_s), frac(n_t, S_r), frac(n_f, S_s)
+    nn = f"1-NN-{distance}-acc"
+    out[nn], out[nn + "_t"], out[nn + "_f"] = frac(n_t + n_f, S_r + S_s), frac(n_t, S_r), frac(n_f, S_s)
     return out
 
 
-def compute_all_metrics(sample_pcs, ref_pcs, batch_size=None):
+def compute_all_metrics(sample_pcs, ref_pcs, batch_size=None, emd=False):
     """MMD, COV and 1-NNA under the Chamfer distance (see distribution_metrics_from_matrices) of the generated clouds
     sample_pcs [S_s, N, 3] against the reference clouds ref_pcs [S_r, M, 3], both GPU tensors. `batch_size` caps the
-    cloud pairs per kernel launch (chamfer_matrix's max_pairs_per_launch). Returns a dict of Python floats."""
+    cloud pairs per kernel launch (chamfer_matrix's and emd_matrix's max_pairs_per_launch). emd=True adds the same six
+    metrics under the EMD (emd_matrix; needs N == M <= 4096), keyed `-EMD`. Returns a dict of Python floats."""
+    if emd:
+        _emd_point_counts([(sample_pcs, "sample_pcs"), (ref_pcs, "ref_pcs")])
     smp, ref = _finite_points((sample_pcs, "sample_pcs"), (ref_pcs, "ref_pcs"))
     if smp.shape[0] == 0 or ref.shape[0] == 0:
         raise ValueError("compute_all_metrics: empty set")
     d_rs = chamfer_matrix(ref, smp, batch_size)
     d_rr = chamfer_matrix(ref, None, batch_size)
     d_ss = chamfer_matrix(smp, None, batch_size)
-    return {k: float(v) for k, v in distribution_metrics_from_matrices(d_rs, d_rr, d_ss).items()}
+    out = {k: float(v) for k, v in distribution_metrics_from_matrices(d_rs, d_rr, d_ss).items()}
+    if emd:
+        m_rs = emd_matrix(ref, smp, batch_size)
+        m_rr = emd_matrix(ref, None, batch_size)
+        m_ss = emd_matrix(smp, None, batch_size)
+        # PointFlow's 1-NN classifier takes each element's nearest neighbour along dim 0 of its pooled matrix
+        # [[M_rr, M_rs], [M_rs^T, M_ss]] (element j is the second argument of the EMD). The pooled matrix of the
+        # transposed blocks is the transpose of that one, so the row rule of distribution_metrics_from_matrices on
+        # (M_rs, M_rr^T, M_ss^T) is PointFlow's rule; MMD and COV use M_rs as it stands, as PointFlow does.
+        out.update({k: float(v) for k, v in distribution_metrics_from_matrices(m_rs, m_rr.t(), m_ss.t(), distance="EMD").items()})
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------

@@ -1,11 +1,13 @@
 """Set-level quality of generated point clouds against a reference set: MMD, COV and 1-NNA under the Chamfer distance.
 
-    python scripts/eval_pointsets.py SAMPLES REFS [--out FILE]
+    python scripts/eval_pointsets.py SAMPLES REFS [--emd] [--out FILE]
 
 SAMPLES and REFS are each a `.npy` holding [S, n, 3] (what `bench.py --dump-outputs DIR` writes as DIR/points.npy) or a
 directory of per-cloud [n, 3] `.npy` files (what metrics.save_point_clouds writes). Points are used as given: normalise
 both sets the same way first (e.g. metrics.GlobalNormalizer). Prints one JSON line with the six metrics
-(metrics.distribution_metrics_from_matrices), the set sizes and the seconds taken; --out writes the same line to FILE.
+(metrics.distribution_metrics_from_matrices), the set sizes and the seconds taken; --emd adds the same six metrics under
+the EMD (approxmatch, metrics.emd_matrix; equal point counts, at most 4096), keyed `-EMD`; --out writes the same line to
+FILE.
 Runs on the GPU only (the all-pairs Chamfer matrices are HIP kernels) and fails without one.
 """
 import argparse
@@ -28,6 +30,7 @@ def main(argv=None):
     ap.add_argument("samples", help="generated clouds: [S, n, 3] .npy or a directory of [n, 3] .npy files")
     ap.add_argument("refs", help="reference clouds: [S, n, 3] .npy or a directory of [n, 3] .npy files")
     ap.add_argument("--out", help="also write the JSON line to this file")
+    ap.add_argument("--emd", action="store_true", help="also the six metrics under the EMD (approxmatch)")
     ap.add_argument("--batch-size", type=int, default=None, help="cloud pairs per kernel launch (default: the library's cap)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -36,7 +39,7 @@ def main(argv=None):
     ref = torch.from_numpy(metrics.load_point_clouds(args.refs)).cuda()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    res = metrics.compute_all_metrics(smp, ref, batch_size=args.batch_size)
+    res = metrics.compute_all_metrics(smp, ref, batch_size=args.batch_size, emd=args.emd)
     res.update({"n_samples": smp.shape[0], "n_refs": ref.shape[0], "sample_points": smp.shape[1], "ref_points": ref.shape[1],
                 "seconds": round(time.perf_counter() - t0, 4)})
     line = json.dumps(res)
