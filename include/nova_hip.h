@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NOVA_HIP_VERSION 403 /* 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
+#define NOVA_HIP_VERSION 404 /* 0.4.4: nova_pointset_occupancy_grid (occupancy grid of a cloud set for the JSD metric); 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
 
 typedef enum { NOVA_F32 = 0, NOVA_BF16 = 1, NOVA_F16 = 2 } nova_dtype;
 typedef enum { NOVA_ACT_NONE = 0, NOVA_ACT_GELU_ERF = 1, NOVA_ACT_SILU = 2 } nova_act;
@@ -279,6 +279,38 @@ int nova_pointset_chamfer_matrix(const float* x, const float* y, float* cd, int 
  * NOVA_ERR_ARG for null pointers (A, B > 0), ldc < B, N < 1 or N > NOVA_EMD_MAX_POINTS. Coordinates must be finite. */
 #define NOVA_EMD_MAX_POINTS 4096
 int nova_pointset_emd_matrix(const float* x, const float* y, float* emd, int A, int B, int N, int ldc, void* stream);
+
+/* Occupancy grid of a set of clouds x [S, N, 3] (float32) for the JSD metric of the point-cloud generation literature
+ * (PointFlow's jsd_between_point_cloud_sets / entropy_of_occupancy_grid; restated from the published algorithm, parity
+ * unpinned by execution). For a resolution R the lattice nodes are
+ *   c(i, j, k) = (i, j, k) / (R - 1) - 0.5,  i, j, k in 0 .. R-1,  flat index (i R + j) R + k.
+ * With in_sphere != 0 the grid is the subset of nodes with |c| <= 0.5, decided in integers:
+ *   (2i - (R-1))^2 + (2j - (R-1))^2 + (2k - (R-1))^2 <= (R-1)^2
+ * (10144 nodes at R = 28). PointFlow decides it with a float32 norm: for even R no node lies on the sphere and the two
+ * rules give the same grid; for odd R they may differ on boundary nodes (8 nodes at R = 27 and 29), and the integer
+ * rule is the definition here. With in_sphere == 0 the grid is the whole lattice. Each point is assigned to its nearest
+ * grid node (Euclidean; a point outside the ball or cube still goes to the nearest node of the grid), and
+ *   counters[node]  += number of points, over all S clouds, assigned to the node
+ *   bernoulli[node] += number of clouds with at least one point assigned to the node
+ * Both are int64 [R^3] (zero stays zero off the grid) and are ADDED TO: the caller zeroes them, and may split a set over
+ * several calls. bernoulli may be NULL. node (optional, NULL: not written) is int32 [S, N], each point's flat node index.
+ * outside (optional, NULL: not written) is one int64 counter, added to: the points whose rounded node (below) is not a
+ * grid node, i.e. that lie outside the grid's cells.
+ * Float32 expressions the results rest on:
+ *   node coordinate per axis   c_i = (float)(2 i - (R-1)) / (float)(2 (R-1))          one IEEE division, error <= 3e-8
+ *   rounded node per axis      clamp(rintf((p + 0.5f) * (float)(R-1)), 0, R-1)         one add, one multiply, both rounded
+ * When the rounded node is a grid node it is the point's node. Otherwise the node is the minimum over candidate grid
+ * nodes (one per lattice column (i, j): k = the rounded k clamped into the column's grid nodes; the columns within the
+ * distance to a known grid node; csrc/occupancy.hip proves that the nearest node is among them) of the float32 squared
+ * distance fma(e2, e2, fma(e1, e1, e0 * e0)), e = p - c. Ties (not defined by the reference): the lowest flat index
+ * among the candidates at the minimum of that float32 distance.
+ * All results are integers: exact, and the same for every split over calls, grid size and run. workgroups: 0 = automatic,
+ * > 0 = split the S clouds over (at least) that many workgroups (a workgroup holds at most 255 clouds and 2^24 - 1 points).
+ * NOVA_ERR_SHAPE for N <= 0 or N >= 2^24; NOVA_ERR_ARG for R outside 2 .. NOVA_OCC_MAX_RES, R == 2 with in_sphere (no node
+ * inside the ball), workgroups < 0, and null x or counters (S > 0). S <= 0 is a no-op. Coordinates must be finite. */
+#define NOVA_OCC_MAX_RES 32
+int nova_pointset_occupancy_grid(const float* x, long long* counters, long long* bernoulli, int* node, long long* outside, int S,
+                                 int N, int R, int in_sphere, int workgroups, void* stream);
 
 /* ---- composite entry points (what the AR loop actually calls) --------------------------------
  * One ViT block's parameters (reference state_dict names in comments). GEMM weights in `dtype`,

@@ -475,6 +475,11 @@ int nova_pointset_emd_matrix(const float* x, const float* y, float* emd, int A, 
   return pointset_emd_matrix(x, y, emd, A, B, N, ldc, (hipStream_t)stream);
 }
 
+int nova_pointset_occupancy_grid(const float* x, long long* counters, long long* bernoulli, int* node, long long* outside, int S,
+                                 int N, int R, int in_sphere, int workgroups, void* stream) {
+  return pointset_occupancy_grid(x, counters, bernoulli, node, outside, S, N, R, in_sphere, workgroups, (hipStream_t)stream);
+}
+
 int nova_modulate_rows(const void* x, const void* mod, void* out, long rows, int D, int dtype, void* stream) {
   NOVA_REQUIRE(!bad_dtype(dtype), NOVA_ERR_ARG, "modulate_rows: bad dtype %d", dtype);
   NOVA_REQUIRE(rows == 0 || (x && mod && out), NOVA_ERR_ARG, "modulate_rows: null pointer");

@@ -150,5 +150,8 @@ int pointset_chamfer_matrix(const float* x, const float* y, float* cd, int A, in
                             hipStream_t st);
 // ---- emd.hip (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA; point counts 1 .. EMD_MAX_N)
 int pointset_emd_matrix(const float* x, const float* y, float* emd, int A, int B, int N, int ldc, hipStream_t st);
+// ---- occupancy.hip (occupancy grid of a cloud set for the JSD metric; resolutions 2 .. NOVA_OCC_MAX_RES)
+int pointset_occupancy_grid(const float* x, long long* counters, long long* bernoulli, int* node, long long* outside, int S, int N,
+                            int R, int in_sphere, int workgroups, hipStream_t st);
 
 }  // namespace nova

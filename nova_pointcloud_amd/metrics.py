@@ -15,6 +15,11 @@ compute_all_metrics, and load_point_clouds for what save_point_clouds or `bench.
 metrics under the EMD of that literature (compute_all_metrics(..., emd=True)) run on emd_matrix (csrc/emd.hip): the
 approximate matching of Fan et al. ("approxmatch", PointFlow's emd_approx), not the exact assignment of
 compute_emd_distance above. It is asymmetric, so the full matrices are computed and oriented as PointFlow orients them.
+
+The seventh column of those tables, the JSD between the two sets' occupancy distributions on a 28^3 grid in the ball of
+radius 0.5: occupancy_grid (csrc/occupancy.hip), entropy_of_occupancy_grid, jensen_shannon_divergence,
+jsd_between_point_cloud_sets and compute_all_metrics(..., jsd=True). The grid is fixed in space, so the JSD depends on
+how the clouds are normalised: normalize_clouds puts each cloud into that ball or cube.
 """
 import json
 import math
@@ -286,11 +291,15 @@ def distribution_metrics_from_matrices(d_rs, d_rr, d_ss, distance="CD"):
     return out
 
 
-def compute_all_metrics(sample_pcs, ref_pcs, batch_size=None, emd=False):
+def compute_all_metrics(sample_pcs, ref_pcs, batch_size=None, emd=False, jsd=False, jsd_resolution=28):
     """MMD, COV and 1-NNA under the Chamfer distance (see distribution_metrics_from_matrices) of the generated clouds
     sample_pcs [S_s, N, 3] against the reference clouds ref_pcs [S_r, M, 3], both GPU tensors. `batch_size` caps the
     cloud pairs per kernel launch (chamfer_matrix's and emd_matrix's max_pairs_per_launch). emd=True adds the same six
-    metrics under the EMD (emd_matrix; needs N == M <= 4096), keyed `-EMD`. Returns a dict of Python floats."""
+    metrics under the EMD (emd_matrix; needs N == M <= 4096), keyed `-EMD`. jsd=True adds "jsd"
+    (jsd_between_point_cloud_sets at `jsd_resolution`; expects the clouds in the ball of radius 0.5) and
+    "jsd_outside_fraction", the larger of the two sets' shares of points outside the grid. Returns a dict of Python floats."""
+    if jsd:
+        _check_resolution(jsd_resolution, True)
     if emd:
         _emd_point_counts([(sample_pcs, "sample_pcs"), (ref_pcs, "ref_pcs")])
     smp, ref = _finite_points((sample_pcs, "sample_pcs"), (ref_pcs, "ref_pcs"))
@@ -309,7 +318,149 @@ def compute_all_metrics(sample_pcs, ref_pcs, batch_size=None, emd=False):
         # transposed blocks is the transpose of that one, so the row rule of distribution_metrics_from_matrices on
         # (M_rs, M_rr^T, M_ss^T) is PointFlow's rule; MMD and COV use M_rs as it stands, as PointFlow does.
         out.update({k: float(v) for k, v in distribution_metrics_from_matrices(m_rs, m_rr.t(), m_ss.t(), distance="EMD").items()})
+    if jsd:
+        o_s, o_r = occupancy_grid(smp, jsd_resolution, True), occupancy_grid(ref, jsd_resolution, True)
+        out["jsd"] = float(jensen_shannon_divergence(o_s["counters"], o_r["counters"]))
+        out["jsd_outside_fraction"] = max(o_s["outside"] / (smp.shape[0] * smp.shape[1]), o_r["outside"] / (ref.shape[0] * ref.shape[1]))
     return out
+
+
+# ----------------------------------------------------------------------------------------------------
+# JSD between the occupancy distributions of two sets
+# ----------------------------------------------------------------------------------------------------
+OCC_MAX_RESOLUTION = 32  # == NOVA_OCC_MAX_RES of include/nova_hip.h
+_OCC_POINTS_PER_LAUNCH = 1 << 24  # ~1.7e7 points: 10 ms per launch when every point takes the slow path over the whole grid (profiles/occupancy_grid_*)
+
+
+def _check_resolution(resolution, in_sphere):
+    if not isinstance(resolution, int) or isinstance(resolution, bool) or not 2 <= resolution <= OCC_MAX_RESOLUTION:
+        raise ValueError(f"resolution must be an integer in 2 .. {OCC_MAX_RESOLUTION}, got {resolution!r}")
+    if in_sphere and resolution == 2:
+        raise ValueError("resolution 2 has no node inside the ball of radius 0.5 (in_sphere)")
+
+
+def grid_node_mask(resolution=28, in_sphere=True):
+    """bool [R^3] (CPU): which lattice nodes c(i, j, k) = (i, j, k) / (R - 1) - 0.5, flat index (i R + j) R + k, belong to
+    the grid. in_sphere keeps |c| <= 0.5, decided in integers: (2i-(R-1))^2 + (2j-(R-1))^2 + (2k-(R-1))^2 <= (R-1)^2
+    (10144 nodes at R = 28; include/nova_hip.h, nova_pointset_occupancy_grid)."""
+    _check_resolution(resolution, in_sphere)
+    R = resolution
+    if not in_sphere:
+        return torch.ones(R ** 3, dtype=torch.bool)
+    t2 = (2 * torch.arange(R, dtype=torch.int64) - (R - 1)) ** 2
+    return ((t2[:, None, None] + t2[None, :, None] + t2[None, None, :]) <= (R - 1) ** 2).reshape(-1)
+
+
+def occupancy_grid(pclouds, resolution=28, in_sphere=True, return_nodes=False, max_clouds_per_launch=None, workgroups=0):
+    """Occupancy of the R^3 lattice over [-0.5, 0.5]^3 (in_sphere: of its nodes inside the ball of radius 0.5) by the
+    clouds pclouds [S, N, 3] on the GPU: every point goes to its nearest grid node (a point outside the ball or cube
+    too). Returns a dict with
+
+        counters   int64 [R^3] on the input's device: points per node over all clouds (flat index (i R + j) R + k)
+        bernoulli  int64 [R^3]: clouds with at least one point on the node
+        outside    int: points whose own cell (the per-axis rounded node) is not a grid node, i.e. outside the ball or cube
+        nodes      int32 [S, N], each point's node (only with return_nodes=True)
+
+    The definition, the tie rule and the float32 expressions are in include/nova_hip.h at nova_pointset_occupancy_grid.
+    The grid is fixed in space: normalise the clouds first (normalize_clouds). All results are integers and are the same
+    for every split: the set goes out in launches of at most `max_clouds_per_launch` clouds (default:
+    _OCC_POINTS_PER_LAUNCH points each), and `workgroups` (0 = automatic) sets the kernel's grid size."""
+    _check_resolution(resolution, in_sphere)
+    (x,) = _finite_points((pclouds, "pclouds"))
+    S, N, R = x.shape[0], x.shape[1], resolution
+    counters = torch.zeros(R ** 3, dtype=torch.int64, device=x.device)
+    bernoulli = torch.zeros_like(counters)
+    outside = torch.zeros(1, dtype=torch.int64, device=x.device)
+    nodes = torch.empty(S, N, dtype=torch.int32, device=x.device) if return_nodes else None
+    if S > 0:
+        if N == 0:
+            raise ValueError("occupancy_grid: empty clouds (0 points)")
+        per = max_clouds_per_launch if max_clouds_per_launch is not None else max(1, _OCC_POINTS_PER_LAUNCH // N)
+        if per < 1:
+            raise ValueError(f"max_clouds_per_launch must be >= 1, got {per}")
+        with torch.cuda.device(x.device):
+            st = hip.stream_ptr()
+            for s0 in range(0, S, per):
+                s1 = min(S, s0 + per)
+                hip.call("nova_pointset_occupancy_grid", x[s0].data_ptr(), counters.data_ptr(), bernoulli.data_ptr(),
+                         nodes[s0].data_ptr() if return_nodes else None, outside.data_ptr(), s1 - s0, N, R, 1 if in_sphere else 0,
+                         int(workgroups), st)
+    out = {"counters": counters, "bernoulli": bernoulli, "outside": int(outside)}
+    if return_nodes:
+        out["nodes"] = nodes
+    return out
+
+
+def entropy_of_occupancy_grid(pclouds, grid_resolution=28, in_sphere=True):
+    """(acc_entropy, counters) of PointFlow's entropy_of_occupancy_grid, restated from the published algorithm (parity
+    unpinned by execution): counters int64 [R^3] as occupancy_grid returns them, and acc_entropy (float) the sum over
+    the nodes with bernoulli > 0 of the entropy H([p, 1 - p]) (natural log, p = bernoulli / S), divided by the number of
+    grid nodes. Odd resolutions with in_sphere may differ from PointFlow's grid on boundary nodes (its membership test is
+    a float32 norm; ours is the integer rule of grid_node_mask); even ones, the default 28 among them, do not."""
+    occ = occupancy_grid(pclouds, grid_resolution, in_sphere)
+    S = pclouds.shape[0]
+    if S == 0:
+        raise ValueError("entropy_of_occupancy_grid: empty set")
+    p = occ["bernoulli"].double() / S
+    p = p[p > 0]
+    h = -(torch.xlogy(p, p) + torch.xlogy(1 - p, 1 - p)).sum()
+    return float(h) / int(grid_node_mask(grid_resolution, in_sphere).sum()), occ["counters"]
+
+
+def _entropy_base2(p):
+    return -torch.xlogy(p, p).sum() / math.log(2.0)
+
+
+def jensen_shannon_divergence(P, Q):
+    """JSD(P, Q) = H2((P' + Q') / 2) - (H2(P') + H2(Q')) / 2 of two histograms of equal size, P' = P / sum P,
+    Q' = Q / sum Q, H2 the base-2 entropy with 0 log 0 = 0 (PointFlow's jensen_shannon_divergence). Pure tensor logic in
+    float64, CPU or GPU: a 0-dim float64 tensor in [0, 1] on P's device. ValueError for negative values, unequal sizes or an
+    all-zero histogram."""
+    P, Q = torch.as_tensor(P), torch.as_tensor(Q)
+    if P.numel() != Q.numel():
+        raise ValueError(f"histograms of unequal size ({P.numel()} and {Q.numel()})")
+    P, Q = P.reshape(-1).double(), Q.to(P.device).reshape(-1).double()
+    if bool((P < 0).any()) or bool((Q < 0).any()):
+        raise ValueError("negative values")
+    if not (float(P.sum()) > 0 and float(Q.sum()) > 0):
+        raise ValueError("all-zero histogram")
+    P_, Q_ = P / P.sum(), Q / Q.sum()
+    res = _entropy_base2((P_ + Q_) / 2) - (_entropy_base2(P_) + _entropy_base2(Q_)) / 2
+    return res.clamp(0.0, 1.0)
+
+
+def jsd_between_point_cloud_sets(sample_pcs, ref_pcs, resolution=28):
+    """JSD between the occupancy distributions (the counters of the in-sphere grid at `resolution`) of the generated
+    clouds and the reference clouds, both [S, n, 3] GPU tensors expected in the ball of radius 0.5 (normalize_clouds):
+    PointFlow's jsd_between_point_cloud_sets, restated from the published algorithm (parity unpinned by execution).
+    Returns a Python float in [0, 1]."""
+    smp = occupancy_grid(sample_pcs, resolution, True)
+    ref = occupancy_grid(ref_pcs, resolution, True)
+    return float(jensen_shannon_divergence(smp["counters"], ref["counters"]))
+
+
+NORMALIZE_MODES = ("none", "unit_sphere", "unit_cube")
+
+
+def normalize_clouds(points, mode):
+    """Per-cloud normalisation of points [..., n, 3] (pure torch, CPU or GPU) into the region the occupancy grid covers:
+        "unit_sphere"  subtract the centre of the bounding box, divide by twice the largest remaining norm: |p| <= 0.5
+        "unit_cube"    subtract the same centre, divide by the longest box side: every coordinate in [-0.5, 0.5]
+        "none"         the input itself
+    A degenerate cloud (all points equal) maps to the origin."""
+    if mode not in NORMALIZE_MODES:
+        raise ValueError(f"mode must be one of {NORMALIZE_MODES}, got {mode!r}")
+    if mode == "none":
+        return points
+    if points.dim() < 2 or points.shape[-1] != 3 or points.shape[-2] == 0:
+        raise ValueError(f"expected [..., n, 3] points with n >= 1, got {tuple(points.shape)}")
+    hi, lo = points.max(dim=-2, keepdim=True).values, points.min(dim=-2, keepdim=True).values
+    centred = points - (hi + lo) / 2
+    if mode == "unit_sphere":
+        scale = 2 * centred.norm(dim=-1, keepdim=True).max(dim=-2, keepdim=True).values
+    else:
+        scale = (hi - lo).max(dim=-1, keepdim=True).values
+    return centred / torch.where(scale > 0, scale, torch.ones_like(scale))
 
 
 # ----------------------------------------------------------------------------------------------------

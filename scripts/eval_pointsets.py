@@ -1,13 +1,15 @@
 """Set-level quality of generated point clouds against a reference set: MMD, COV and 1-NNA under the Chamfer distance.
 
-    python scripts/eval_pointsets.py SAMPLES REFS [--emd] [--out FILE]
+    python scripts/eval_pointsets.py SAMPLES REFS [--emd] [--jsd] [--normalize MODE] [--out FILE]
 
 SAMPLES and REFS are each a `.npy` holding [S, n, 3] (what `bench.py --dump-outputs DIR` writes as DIR/points.npy) or a
 directory of per-cloud [n, 3] `.npy` files (what metrics.save_point_clouds writes). Points are used as given: normalise
 both sets the same way first (e.g. metrics.GlobalNormalizer). Prints one JSON line with the six metrics
 (metrics.distribution_metrics_from_matrices), the set sizes and the seconds taken; --emd adds the same six metrics under
-the EMD (approxmatch, metrics.emd_matrix; equal point counts, at most 4096), keyed `-EMD`; --out writes the same line to
-FILE.
+the EMD (approxmatch, metrics.emd_matrix; equal point counts, at most 4096), keyed `-EMD`; --jsd adds "jsd", the
+Jensen-Shannon divergence between the two sets' occupancy distributions on a 28^3 grid (--jsd-resolution R) in the ball of
+radius 0.5, and "jsd_outside_fraction"; --normalize unit_sphere / unit_cube (metrics.normalize_clouds) puts every cloud of
+both sets into that ball / cube before all metrics; --out writes the same line to FILE.
 Runs on the GPU only (the all-pairs Chamfer matrices are HIP kernels) and fails without one.
 """
 import argparse
@@ -31,6 +33,10 @@ def main(argv=None):
     ap.add_argument("refs", help="reference clouds: [S, n, 3] .npy or a directory of [n, 3] .npy files")
     ap.add_argument("--out", help="also write the JSON line to this file")
     ap.add_argument("--emd", action="store_true", help="also the six metrics under the EMD (approxmatch)")
+    ap.add_argument("--jsd", action="store_true", help="also the JSD between the occupancy distributions of the two sets")
+    ap.add_argument("--jsd-resolution", type=int, default=28, metavar="R", help="grid resolution of the JSD (default 28)")
+    ap.add_argument("--normalize", choices=metrics.NORMALIZE_MODES, default=None,
+                    help="per-cloud normalisation of both sets before all metrics (default: none)")
     ap.add_argument("--batch-size", type=int, default=None, help="cloud pairs per kernel launch (default: the library's cap)")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -39,7 +45,15 @@ def main(argv=None):
     ref = torch.from_numpy(metrics.load_point_clouds(args.refs)).cuda()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    res = metrics.compute_all_metrics(smp, ref, batch_size=args.batch_size, emd=args.emd)
+    if args.normalize is not None:
+        smp, ref = metrics.normalize_clouds(smp, args.normalize), metrics.normalize_clouds(ref, args.normalize)
+    extra = {"jsd": True, "jsd_resolution": args.jsd_resolution} if args.jsd else {}
+    res = metrics.compute_all_metrics(smp, ref, batch_size=args.batch_size, emd=args.emd, **extra)
+    if args.normalize is not None:
+        res["normalize"] = args.normalize
+    if res.get("jsd_outside_fraction", 0.0) > 0.05:
+        print(f"warning: {100 * res['jsd_outside_fraction']:.1f} % of the points of a set lie outside the JSD grid: the clouds are not "
+              "in the unit ball (radius 0.5); normalise them, e.g. with --normalize unit_sphere", file=sys.stderr)
     res.update({"n_samples": smp.shape[0], "n_refs": ref.shape[0], "sample_points": smp.shape[1], "ref_points": ref.shape[1],
                 "seconds": round(time.perf_counter() - t0, 4)})
     line = json.dumps(res)
