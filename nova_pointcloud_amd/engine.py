@@ -360,8 +360,7 @@ class NovaEngine(object):
         rope_q = hip.rope_table(pos_img, pred_ids, 0, inv_freq, B, hd, out=ws["rope_q"]) if pos_img is not None else None
         hip.call("nova_qkv_rope_cols", xq.data_ptr(), lp.q[0], lp.q[1], hip.ptr(rope_q), q.data_ptr(), S * n, D, D, n,
                  B if rope_q is not None else 1, hd, D, code, st())
-        hip.call("nova_attn_fwd", q.data_ptr(), kv.data_ptr(), kv.data_ptr() + D * es, o.data_ptr(), S, self.heads, n, L, hd,
-                 D, 2 * D, D, float(hd) ** -0.5, code, st())
+        hip.attn_fwd(q, kv, kv, o, S, self.heads, n, L, hd, D, 2 * D, D, v_off=D)
         self._gemm(o, lp.proj[0], lp.proj[1], D, out=a)
         hip.call("nova_row_norm", a.data_ptr(), xq.data_ptr(), lp.n1[0], lp.n1[1], None, 0, -1, -1, -1, xq.data_ptr(), None, S * n,
                  D, 1e-5, code, st())

@@ -255,16 +255,56 @@ def rope_table(pos, ids, pad, inv_freq, nb, hd, out=None):
     return out
 
 
+def attn_fwd(q, k, v, out, S, heads, Lq, Lk, hd, q_rs, kv_rs, o_rs, scale=None, k_off=0, v_off=0):
+    """nova_attn_fwd on buffers of any row stride (in elements): q rows [S*Lq] with stride q_rs, k / v rows [S*Lk] with
+    stride kv_rs starting k_off / v_off elements into their tensors (k and v may share one tensor, or all three: the
+    packed [.., 3D] buffer, the k | v rows [.., 2D] of the last encoder block or of a cache), o rows with stride o_rs.
+    scale None = head_dim ** -0.5."""
+    es = q.element_size()
+    assert k.dtype == q.dtype and v.dtype == q.dtype and out.dtype == q.dtype
+    call("nova_attn_fwd", ptr(q), ptr(k) + k_off * es, ptr(v) + v_off * es, ptr(out), S, heads, Lq, Lk, hd, q_rs, kv_rs, o_rs,
+         float(hd) ** -0.5 if scale is None else float(scale), dtype_code(q.dtype), stream_ptr())
+    return out
+
+
 def attn_fwd_packed(qkv, S, L, heads, out=None):
     """Attention reading q/k/v in place from the fused [S*L, 3D] buffer; returns merged heads [S*L, D]."""
     D = qkv.shape[-1] // 3
-    hd = D // heads
     out = qkv.new_empty(S * L, D) if out is None else out
-    es = qkv.element_size()
-    base = ptr(qkv)
-    call("nova_attn_fwd", base, base + D * es, base + 2 * D * es, ptr(out), S, heads, L, L, hd, 3 * D, 3 * D, D,
-         float(hd) ** -0.5, dtype_code(qkv.dtype), stream_ptr())
+    return attn_fwd(qkv, qkv, qkv, out, S, heads, L, L, D // heads, 3 * D, 3 * D, D, k_off=D, v_off=2 * D)
+
+
+def qkv_rope_cols(x, w, bias, rope, L, hd, rope_cols, out=None):
+    """out[M,N] = x[M,K] @ w[N,K]^T + bias with columns [0, rope_cols) rotated by rope[(m // L) % nb, m % L]
+    (rope [nb, L, hd/2, 2] f32, or None with rope_cols = 0: the plain projection)."""
+    M, K = x.shape
+    N = w.shape[0]
+    assert w.shape[1] == K and w.dtype == x.dtype
+    if rope is not None:
+        assert rope.shape[1] == L and rope.shape[2] * 2 == hd
+    out = x.new_empty(M, N) if out is None else out
+    call("nova_qkv_rope_cols", ptr(x), ptr(w), ptr(bias, torch.float32), ptr(rope, torch.float32), ptr(out), M, N, K, L,
+         rope.shape[0] if rope is not None else 1, hd, rope_cols, dtype_code(x.dtype), stream_ptr())
     return out
+
+
+def modulate_rows(x, mod, out=None):
+    """out[r] = x[r] * (1 + mod[r, :D]) + mod[r, D:2D] for x [rows, D], mod [rows, 2D]; out may be x (in place)."""
+    rows, D = x.shape
+    assert mod.shape == (rows, 2 * D) and mod.dtype == x.dtype
+    out = torch.empty_like(x) if out is None else out
+    call("nova_modulate_rows", ptr(x), ptr(mod), ptr(out), rows, D, dtype_code(x.dtype), stream_ptr())
+    return out
+
+
+def vit_blocks_forward_kv(blocks, x, S, L, heads, hidden, rope, cache, cache_cap, cache_len, ws_qkv, ws_a, ws_b, ws_h):
+    """nova_vit_blocks_forward_kv on x [S*L, D] in place: `blocks` a VitBlock array, cache [nblocks, S, cache_cap, 2D],
+    rope [nb, L, hd/2, 2] f32 for the L new rows or None. The caller advances cache_len by L."""
+    D = x.shape[-1]
+    call("nova_vit_blocks_forward_kv", blocks, len(blocks), ptr(x), S, L, D, heads, hidden, ptr(rope, torch.float32),
+         rope.shape[0] if rope is not None else 1, ptr(cache), cache_cap, cache_len, ptr(ws_qkv), ptr(ws_a), ptr(ws_b),
+         ptr(ws_h), dtype_code(x.dtype), stream_ptr())
+    return x
 
 
 def row_norm(x, out=None, gamma=None, beta=None, mod=None, scale_off=-1, shift_off=-1, gate_off=-1, res=None,
