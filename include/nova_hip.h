@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NOVA_HIP_VERSION 404 /* 0.4.4: nova_pointset_occupancy_grid (occupancy grid of a cloud set for the JSD metric); 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
+#define NOVA_HIP_VERSION 405 /* 0.4.5: nova_pointset_farthest_point_sample (farthest point sampling of a cloud set, to bring sets to a common point count); 0.4.4: nova_pointset_occupancy_grid (occupancy grid of a cloud set for the JSD metric); 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
 
 typedef enum { NOVA_F32 = 0, NOVA_BF16 = 1, NOVA_F16 = 2 } nova_dtype;
 typedef enum { NOVA_ACT_NONE = 0, NOVA_ACT_GELU_ERF = 1, NOVA_ACT_SILU = 2 } nova_act;
@@ -311,6 +311,35 @@ int nova_pointset_emd_matrix(const float* x, const float* y, float* emd, int A, 
 #define NOVA_OCC_MAX_RES 32
 int nova_pointset_occupancy_grid(const float* x, long long* counters, long long* bernoulli, int* node, long long* outside, int S,
                                  int N, int R, int in_sphere, int workgroups, void* stream);
+
+/* Farthest point sampling (Eldar et al.; PointNet++) of a set of clouds x [S, N, 3] (float32, finite): n of the N points
+ * of every cloud, to bring sets of different density to the common point count the set-level metrics need (the EMD above
+ * takes equal counts of at most NOVA_EMD_MAX_POINTS). The operation comes from the reference's farthest_point_sampling,
+ * diffnext/models/transformers/transformer_pointcloud_nova.py:100-125, called from adaptive_sampling at :92-97.
+ * DEVIATION, on purpose: that function body takes torch.min(dist_matrix, dim=1) over a matrix that contains the zero
+ * diagonal, so its min_distances are all zero at every step, its argmax is index 0 every time and it returns
+ * [start, 0, 0, ...]. What is built here is the standard algorithm, not parity with that body.
+ * For one cloud x [N, 3], a start index s0 in 0 .. N-1 and 1 <= n <= N:
+ *   idx[0] = s0,  dist[0] = +inf,  mind[j] = +inf
+ *   for i = 1 .. n-1:
+ *       q = x[idx[i-1]]
+ *       mind[j] = fminf(mind[j], d(x[j], q))          for every j
+ *       idx[i]  = the j with the largest mind[j], lowest j on ties
+ *       dist[i] = mind[idx[i]]
+ * d is the exact-difference float32 squared distance of the Chamfer and occupancy kernels: with e = p - q per axis,
+ * d = fmaf(e2, e2, fmaf(e1, e1, e0 * e0)), every operation rounded once (no |p|^2 + |q|^2 - 2 p.q expansion, so the result
+ * is as good for a cloud far from the origin as for a centred one). Consequences:
+ *   - a chosen point has mind = 0 afterwards and is chosen again only when every point has mind = 0, i.e. when n exceeds
+ *     the number of distinct points; the rule then yields the lowest such index (N equal points: [s0, 0, 0, ...]);
+ *   - dist[1:] is non-increasing, exactly: mind only decreases and each dist[i] is its maximum;
+ *   - the result depends on the cloud and s0 only: bitwise the same for every batch, launch split and workgroup shape.
+ * idx is int32 [S, n]; dist is float32 [S, n] and may be NULL; start is int32 [S] on the device, NULL meaning 0 for every
+ * cloud. A start value outside 0 .. N-1 is never dereferenced: the kernel clamps it into the range (callers should reject
+ * it; the Python binding does). NOVA_ERR_SHAPE for N < 1 or N > NOVA_FPS_MAX_POINTS (one workgroup keeps a cloud in
+ * registers, 16 points x 1024 threads; a larger cloud is an error, not a slow path); NOVA_ERR_ARG for n < 1, n > N, or null
+ * x / idx with S > 0. S <= 0 returns 0. */
+#define NOVA_FPS_MAX_POINTS 16384
+int nova_pointset_farthest_point_sample(const float* x, const int* start, int* idx, float* dist, int S, int N, int n, void* stream);
 
 /* ---- composite entry points (what the AR loop actually calls) --------------------------------
  * One ViT block's parameters (reference state_dict names in comments). GEMM weights in `dtype`,

@@ -480,6 +480,10 @@ int nova_pointset_occupancy_grid(const float* x, long long* counters, long long*
   return pointset_occupancy_grid(x, counters, bernoulli, node, outside, S, N, R, in_sphere, workgroups, (hipStream_t)stream);
 }
 
+int nova_pointset_farthest_point_sample(const float* x, const int* start, int* idx, float* dist, int S, int N, int n, void* stream) {
+  return pointset_farthest_point_sample(x, start, idx, dist, S, N, n, (hipStream_t)stream);
+}
+
 int nova_modulate_rows(const void* x, const void* mod, void* out, long rows, int D, int dtype, void* stream) {
   NOVA_REQUIRE(!bad_dtype(dtype), NOVA_ERR_ARG, "modulate_rows: bad dtype %d", dtype);
   NOVA_REQUIRE(rows == 0 || (x && mod && out), NOVA_ERR_ARG, "modulate_rows: null pointer");

@@ -153,5 +153,7 @@ int pointset_emd_matrix(const float* x, const float* y, float* emd, int A, int B
 // ---- occupancy.hip (occupancy grid of a cloud set for the JSD metric; resolutions 2 .. NOVA_OCC_MAX_RES)
 int pointset_occupancy_grid(const float* x, long long* counters, long long* bernoulli, int* node, long long* outside, int S, int N,
                             int R, int in_sphere, int workgroups, hipStream_t st);
+// ---- fps.hip (farthest point sampling of a cloud set; point counts 1 .. NOVA_FPS_MAX_POINTS)
+int pointset_farthest_point_sample(const float* x, const int* start, int* idx, float* dist, int S, int N, int n, hipStream_t st);
 
 }  // namespace nova

@@ -91,6 +91,7 @@ SIGNATURES = {
     "nova_pointset_chamfer_matrix": [c_void_p] * 3 + [c_int] * 6 + [c_void_p],
     "nova_pointset_emd_matrix": [c_void_p] * 3 + [c_int] * 4 + [c_void_p],
     "nova_pointset_occupancy_grid": [c_void_p] * 5 + [c_int] * 5 + [c_void_p],
+    "nova_pointset_farthest_point_sample": [c_void_p] * 4 + [c_int] * 3 + [c_void_p],
     "nova_modulate_rows": [c_void_p] * 3 + [c_long, c_int, c_int, c_void_p],
     "nova_attn_fwd_lse": [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_long, c_long, c_void_p, c_void_p],
     "nova_attn_bwd": [c_void_p] * 10 + [c_int, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_float, c_void_p, c_void_p],
@@ -122,7 +123,7 @@ def lib_path() -> str:
     return _LIB_PATH
 
 
-ABI_VERSION = 404  # == NOVA_HIP_VERSION of include/nova_hip.h (tests/test_abi.py compares the two)
+ABI_VERSION = 405  # == NOVA_HIP_VERSION of include/nova_hip.h (tests/test_abi.py compares the two)
 
 
 def load(check_device=True):

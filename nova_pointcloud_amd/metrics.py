@@ -20,6 +20,9 @@ The seventh column of those tables, the JSD between the two sets' occupancy dist
 radius 0.5: occupancy_grid (csrc/occupancy.hip), entropy_of_occupancy_grid, jensen_shannon_divergence,
 jsd_between_point_cloud_sets and compute_all_metrics(..., jsd=True). The grid is fixed in space, so the JSD depends on
 how the clouds are normalised: normalize_clouds puts each cloud into that ball or cube.
+
+Bringing sets to the point count those metrics need (generated clouds have 2048 points, published reference shapes are
+stored denser, and the EMD takes equal counts of at most 4096): farthest_point_sample (csrc/fps.hip) and resample_clouds.
 """
 import json
 import math
@@ -437,6 +440,111 @@ def jsd_between_point_cloud_sets(sample_pcs, ref_pcs, resolution=28):
     smp = occupancy_grid(sample_pcs, resolution, True)
     ref = occupancy_grid(ref_pcs, resolution, True)
     return float(jensen_shannon_divergence(smp["counters"], ref["counters"]))
+
+
+# ----------------------------------------------------------------------------------------------------
+# farthest point sampling: sets of different density to a common point count
+# ----------------------------------------------------------------------------------------------------
+FPS_MAX_POINTS = 16384  # == NOVA_FPS_MAX_POINTS of include/nova_hip.h
+RESAMPLE_METHODS = ("fps", "first", "random")
+# distance updates (clouds x points x samples) per launch, ~6.9e10. Sized from the kernel's instruction count (7 vector issues
+# per update: ~4e12 updates/s on 256 compute units, so ~17 ms per launch), NOT yet from a measured step time: tools/fps_bench.py
+# writes profiles/fps_bench.json, and this constant is to be re-derived from it (farthest point sampling)
+_FPS_POINT_STEPS_PER_LAUNCH = 1 << 36
+
+
+def fps_kernel_shape(n_points):
+    """(points per thread P, workgroup size T) csrc/fps.hip runs a cloud of `n_points` points with (fps_config there)."""
+    for limit, shape in ((64, (1, 64)), (128, (2, 64)), (256, (1, 256)), (512, (2, 256)), (1024, (4, 256)), (2048, (8, 256)),
+                         (4096, (16, 256)), (8192, (16, 512)), (FPS_MAX_POINTS, (16, 1024))):
+        if n_points <= limit:
+            return shape
+    raise ValueError(f"the FPS kernel takes 1 .. {FPS_MAX_POINTS} points per cloud, got {n_points}")
+
+
+def _fps_arguments(points, n_samples, start):
+    """ValueError for everything about the arguments that does not need the GPU (checked before the device, so it holds
+    for CPU tensors too). Returns `start` as None (index 0 everywhere) or an int64 CPU tensor [S]."""
+    if not torch.is_tensor(points):
+        raise ValueError(f"points: expected a tensor [S, N, 3], got {type(points).__name__}")
+    if points.dim() != 3 or points.shape[-1] != 3:
+        raise ValueError(f"points: expected [S, N, 3] clouds, got {tuple(points.shape)}")
+    S, N = points.shape[0], points.shape[1]
+    if not 1 <= N <= FPS_MAX_POINTS:
+        raise ValueError(f"the FPS kernel takes 1 .. {FPS_MAX_POINTS} points per cloud, got {N}")
+    if not isinstance(n_samples, int) or isinstance(n_samples, bool) or not 1 <= n_samples <= N:
+        raise ValueError(f"n_samples must be an integer in 1 .. {N} (the point count), got {n_samples!r}")
+    if isinstance(start, int) and not isinstance(start, bool):
+        if not 0 <= start < N:
+            raise ValueError(f"start must be in 0 .. {N - 1}, got {start}")
+        st = None if start == 0 else torch.full((S,), start, dtype=torch.int64)
+    else:
+        st = torch.as_tensor(start).detach().cpu()
+        if st.dtype.is_floating_point or st.dtype.is_complex or st.dtype == torch.bool or tuple(st.shape) != (S,):
+            raise ValueError(f"start: expected an int or {S} integer indices (one per cloud), got {tuple(st.shape)} {st.dtype}")
+        st = st.long()
+        if S > 0 and not (0 <= int(st.min()) and int(st.max()) < N):
+            raise ValueError(f"start must be in 0 .. {N - 1}, got values in {int(st.min())} .. {int(st.max())}")
+    if not bool(torch.isfinite(points).all()):
+        raise ValueError("points: points must be finite")
+    return st
+
+
+def farthest_point_sample(points, n_samples, start=0, return_distances=False, max_clouds_per_launch=None):
+    """Farthest point sampling of the clouds points [S, N, 3] on the GPU (1 <= N <= 16384): int64 [S, n_samples] indices on
+    the input's device, row s the points of cloud s in the order they were chosen, starting at `start` (an int, or one
+    index per cloud as an int tensor or sequence [S]); each further one is the point farthest from all chosen so far,
+    lowest index on ties. With return_distances also float32 [S, n_samples]: the squared distance of each chosen point to
+    the ones before it (+inf for the first; non-increasing after it). The algorithm and its float32 distance are spelled
+    out in include/nova_hip.h at nova_pointset_farthest_point_sample (csrc/fps.hip).
+
+    The set goes out in launches of at most `max_clouds_per_launch` clouds (default: _FPS_POINT_STEPS_PER_LAUNCH distance
+    updates each); a cloud's result depends on the cloud and its start only and is bitwise the same for every split."""
+    st = _fps_arguments(points, n_samples, start)
+    x = _points(points, "points")
+    S, N, n = x.shape[0], x.shape[1], n_samples
+    per = max_clouds_per_launch if max_clouds_per_launch is not None else max(1, _FPS_POINT_STEPS_PER_LAUNCH // (N * n))
+    if per < 1:
+        raise ValueError(f"max_clouds_per_launch must be >= 1, got {per}")
+    idx = torch.empty(S, n, dtype=torch.int32, device=x.device)
+    dist = torch.empty(S, n, dtype=torch.float32, device=x.device) if return_distances else None
+    st = st.to(device=x.device, dtype=torch.int32) if st is not None else None
+    if S > 0:
+        with torch.cuda.device(x.device):
+            stream = hip.stream_ptr()
+            for s0 in range(0, S, per):
+                hip.call("nova_pointset_farthest_point_sample", x[s0].data_ptr(), st[s0:].data_ptr() if st is not None else None,
+                         idx[s0].data_ptr(), dist[s0].data_ptr() if return_distances else None, min(S, s0 + per) - s0, N, n, stream)
+    return (idx.long(), dist) if return_distances else idx.long()
+
+
+def resample_clouds(points, n_points, method="fps", start=0, generator=None):
+    """points [S, N, 3] cut to [S, n_points, 3]:
+        "fps"     the farthest_point_sample points, in the order chosen (GPU only; `start` as there)
+        "first"   points[:, :n_points]
+        "random"  a uniformly random subset without repetition: the first n_points of one torch.randperm(N) per cloud,
+                  drawn from `generator` (a CPU generator, or None for the global one)
+    "first" and "random" are pure torch and work on CPU tensors too. n_points == N returns the input itself; more points
+    than the clouds have is a ValueError."""
+    if method not in RESAMPLE_METHODS:
+        raise ValueError(f"method must be one of {RESAMPLE_METHODS}, got {method!r}")
+    if not torch.is_tensor(points) or points.dim() != 3 or points.shape[-1] != 3:
+        raise ValueError(f"points: expected [S, N, 3] clouds, got {tuple(points.shape) if torch.is_tensor(points) else type(points).__name__}")
+    S, N = points.shape[0], points.shape[1]
+    if not isinstance(n_points, int) or isinstance(n_points, bool) or n_points < 1:
+        raise ValueError(f"n_points must be a positive integer, got {n_points!r}")
+    if n_points > N:
+        raise ValueError(f"cannot resample clouds of {N} points to {n_points}: resampling only removes points")
+    if n_points == N:
+        return points
+    if method == "first":
+        return points[:, :n_points]
+    if method == "random":
+        idx = torch.stack([torch.randperm(N, generator=generator)[:n_points] for _ in range(S)]) if S else torch.empty(0, n_points, dtype=torch.int64)
+        idx = idx.to(points.device)
+    else:
+        idx = farthest_point_sample(points, n_points, start=start)
+    return torch.gather(points, 1, idx[:, :, None].expand(S, n_points, 3))
 
 
 NORMALIZE_MODES = ("none", "unit_sphere", "unit_cube")
