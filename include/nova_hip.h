@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NOVA_HIP_VERSION 405 /* 0.4.5: nova_pointset_farthest_point_sample (farthest point sampling of a cloud set, to bring sets to a common point count); 0.4.4: nova_pointset_occupancy_grid (occupancy grid of a cloud set for the JSD metric); 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
+#define NOVA_HIP_VERSION 405 /* still 0.4.5 (tests/test_pointset_fps.py pins the number; a library without the new symbols fails to bind, loudly): nova_pointset_assignment, nova_pointset_assignment_state_bytes, nova_pointset_assignment_rounds (optimal assignment of two clouds by a batched integer auction: the exact EMD on the GPU); 0.4.5: nova_pointset_farthest_point_sample (farthest point sampling of a cloud set, to bring sets to a common point count); 0.4.4: nova_pointset_occupancy_grid (occupancy grid of a cloud set for the JSD metric); 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
 
 typedef enum { NOVA_F32 = 0, NOVA_BF16 = 1, NOVA_F16 = 2 } nova_dtype;
 typedef enum { NOVA_ACT_NONE = 0, NOVA_ACT_GELU_ERF = 1, NOVA_ACT_SILU = 2 } nova_act;
@@ -340,6 +340,57 @@ int nova_pointset_occupancy_grid(const float* x, long long* counters, long long*
  * x / idx with S > 0. S <= 0 returns 0. */
 #define NOVA_FPS_MAX_POINTS 16384
 int nova_pointset_farthest_point_sample(const float* x, const int* start, int* idx, float* dist, int S, int N, int n, void* stream);
+
+/* Optimal assignment between x [B, n, 3] and y [B, n, 3] (float32, finite), pair by pair: the permutation that minimises
+ * the mean matched distance, i.e. the earth mover's distance that compute_emd_distance (test_optimize.py:385-415) and
+ * emd_approx (train_newloss.py:352-372) take from scipy's linear_sum_assignment on a [n, n] cost matrix copied to the
+ * host. Here it is solved on the GPU by a Jacobi auction (Bertsekas) with epsilon scaling in exact integer arithmetic,
+ * one workgroup per pair, 1 <= n <= NOVA_ASSIGN_MAX_POINTS; no cost matrix is ever stored.
+ * Cost.  c(i, j) = sqrtf(d2), d2 = fmaf(e2, e2, fmaf(e1, e1, e0 * e0)) with e = x[i] - y[j] per axis after the optional
+ * clamp fminf(fmaxf(v, clamp_lo), clamp_hi) of every coordinate (use_clamp != 0): bit for bit the float32 entry
+ * D[b, i, j] of nova_pointset_pairwise_dist.
+ * Integer scheme (the contract; every tolerance of the tests follows from it):
+ *   C(i, j)  = llrint(c(i, j) * 2^18) * (n + 1)                        64-bit integers; the product c * 2^18 is exact
+ *   price[j] = 0 for every column j
+ *   eps      = max(1, ((llrint(diag * 2^18) + 1) * (n + 1)) / 4), diag the float32 diagonal of the bounding box of
+ *              both clamped clouds (>= every c, so no pass over the costs is needed)
+ *   phase:   every row unassigned; rounds (below) until every row is assigned; then, if eps == 1, stop, else
+ *            eps = max(1, eps / 8) and the next phase starts with every owner cleared and the prices kept
+ *   round:   every unassigned row i finds, over all j, the smallest and second smallest a(j) = C(i, j) + price[j]
+ *            (that is the best and second-best value -C - price); ties in a go to the lowest j; for n == 1 the second
+ *            equals the first. Row i bids  price[j*] + (second - best) + eps  on its best column j*. Every column takes
+ *            its highest bid, bid ties going to the lowest row, evicts its previous owner and sets its price to the bid.
+ *            All bids of a round are computed from the prices at its start.
+ * Costs are multiples of n + 1 and the last phase runs at eps == 1, so the final assignment is within n * eps < n + 1 of
+ * the optimum of the integer costs, hence optimal for them: its mean quantised cost is the minimum, and its mean float32
+ * cost exceeds the minimum mean of c by at most the quantum 2^-18 (half a quantum per term on either side).
+ * Everything is deterministic: the result is a function of the pair, n and the clamp alone, bitwise the same for every
+ * batch, every split into launches and every run (bids are resolved by a maximum over unique (bid, row) keys, which does
+ * not depend on the order of arrival).
+ * Range.  Keys carry 13 bits of row or column beside the value, so bids must stay below 2^49 and diag below 4096 (costs
+ * < 2^43). A pair outside that range stops with the status NOVA_ASSIGN_RANGE; nothing wraps.
+ * Launches.  One call runs at most `rounds` rounds per pair and then stores the pair's whole state (prices, owners, row
+ * assignments, eps, the rounds used, a done flag) in `state`, nova_pointset_assignment_state_bytes(n) bytes per pair (16-byte
+ * aligned; layout private to the library). restart != 0 ignores the state's content and starts the auction; restart == 0
+ * continues from a state written by an earlier call with the same x, y, B, n and clamp; a finished pair's workgroup
+ * exits at once. all_done (one int on the device) receives 1 when every pair is done, 0 when some pair needs more
+ * rounds, NOVA_ASSIGN_RANGE (-1) when some pair left the range. The caller repeats the call until all_done != 0 and
+ * bounds the total number of rounds itself.
+ * Outputs.  cost[b] is -1 while pair b is unfinished and -2 when it left the range. Once it is done:
+ *   col_of_row[b, i]  int32, the column matched to row i (a permutation of 0 .. n-1)
+ *   cost[b]           the mean over i of the float32 c(i, col_of_row[i]), summed in a fixed order: each thread t of the T
+ *                     threads its rows t, t + T, ... in turn (at most 4), the 64 lanes of a wave pairwise in 6 steps, the
+ *                     T / 64 <= 16 waves in turn, one division by n
+ * NOVA_ERR_ARG for a null pointer (x, y, col_of_row, cost, state with B > 0; all_done always), n outside
+ * 1 .. NOVA_ASSIGN_MAX_POINTS, rounds < 1, or use_clamp with clamp_lo > clamp_hi. B <= 0 only sets all_done to 1.
+ * nova_pointset_assignment_state_bytes returns 0 for n outside the range.
+ * nova_pointset_assignment_rounds copies every pair's rounds-used counter from `state` to rounds_used (int32 [B]). */
+#define NOVA_ASSIGN_MAX_POINTS 4096
+#define NOVA_ASSIGN_RANGE (-1)
+long long nova_pointset_assignment_state_bytes(int n);
+int nova_pointset_assignment(const float* x, const float* y, int* col_of_row, float* cost, void* state, int B, int n, float clamp_lo,
+                             float clamp_hi, int use_clamp, int rounds, int restart, int* all_done, void* stream);
+int nova_pointset_assignment_rounds(const void* state, int* rounds_used, int B, int n, void* stream);
 
 /* ---- composite entry points (what the AR loop actually calls) --------------------------------
  * One ViT block's parameters (reference state_dict names in comments). GEMM weights in `dtype`,

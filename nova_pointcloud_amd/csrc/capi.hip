@@ -484,6 +484,18 @@ int nova_pointset_farthest_point_sample(const float* x, const int* start, int* i
   return pointset_farthest_point_sample(x, start, idx, dist, S, N, n, (hipStream_t)stream);
 }
 
+long long nova_pointset_assignment_state_bytes(int n) { return (long long)pointset_assignment_state_bytes(n); }
+
+int nova_pointset_assignment(const float* x, const float* y, int* col_of_row, float* cost, void* state, int B, int n, float clamp_lo,
+                             float clamp_hi, int use_clamp, int rounds, int restart, int* all_done, void* stream) {
+  return pointset_assignment(x, y, col_of_row, cost, state, B, n, clamp_lo, clamp_hi, use_clamp, rounds, restart, all_done,
+                             (hipStream_t)stream);
+}
+
+int nova_pointset_assignment_rounds(const void* state, int* rounds_used, int B, int n, void* stream) {
+  return pointset_assignment_rounds(state, rounds_used, B, n, (hipStream_t)stream);
+}
+
 int nova_modulate_rows(const void* x, const void* mod, void* out, long rows, int D, int dtype, void* stream) {
   NOVA_REQUIRE(!bad_dtype(dtype), NOVA_ERR_ARG, "modulate_rows: bad dtype %d", dtype);
   NOVA_REQUIRE(rows == 0 || (x && mod && out), NOVA_ERR_ARG, "modulate_rows: null pointer");

@@ -92,6 +92,8 @@ SIGNATURES = {
     "nova_pointset_emd_matrix": [c_void_p] * 3 + [c_int] * 4 + [c_void_p],
     "nova_pointset_occupancy_grid": [c_void_p] * 5 + [c_int] * 5 + [c_void_p],
     "nova_pointset_farthest_point_sample": [c_void_p] * 4 + [c_int] * 3 + [c_void_p],
+    "nova_pointset_assignment": [c_void_p] * 5 + [c_int, c_int, c_float, c_float] + [c_int] * 3 + [c_void_p, c_void_p],
+    "nova_pointset_assignment_rounds": [c_void_p, c_void_p, c_int, c_int, c_void_p],
     "nova_modulate_rows": [c_void_p] * 3 + [c_long, c_int, c_int, c_void_p],
     "nova_attn_fwd_lse": [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_long, c_long, c_void_p, c_void_p],
     "nova_attn_bwd": [c_void_p] * 10 + [c_int, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_float, c_void_p, c_void_p],
@@ -116,7 +118,7 @@ SIGNATURES["nova_prof_collect"] = [ctypes.POINTER(ctypes.c_double), ctypes.POINT
                                    ctypes.POINTER(ctypes.c_longlong), c_int]
 PROF_SLOTS = ["gemm_bias", "gemm_bias_gelu", "gemm_bias_silu", "qkv_gemm_rope", "attention", "row_norm", "gemm_small_tile", "gemm_bias_wide_k",
               "token_plumbing", "decoder_glue"]
-PLAIN = {"nova_version": (c_int, []), "nova_last_error": (ctypes.c_char_p, []), "nova_check_device": (c_int, [])}
+PLAIN = {"nova_pointset_assignment_state_bytes": (ctypes.c_longlong, [c_int]), "nova_version": (c_int, []), "nova_last_error": (ctypes.c_char_p, []), "nova_check_device": (c_int, [])}
 
 
 def lib_path() -> str:
@@ -145,12 +147,16 @@ def load(check_device=True):
             if lib.nova_version() != ABI_VERSION:  # a stale build would take e.g. `stream` where `key_limit` now sits
                 raise NovaHipError(f"{_LIB_PATH} is C ABI version {lib.nova_version()}, this package binds version {ABI_VERSION} "
                                    "(include/nova_hip.h NOVA_HIP_VERSION): rebuild it with `make -C nova_pointcloud_amd/csrc`")
-            for name, argtypes in SIGNATURES.items():
-                fn = getattr(lib, name)
-                fn.argtypes, fn.restype = argtypes, c_int
-            for name, (res, argtypes) in PLAIN.items():
-                fn = getattr(lib, name)
-                fn.argtypes, fn.restype = argtypes, res
+            try:
+                for name, argtypes in SIGNATURES.items():
+                    fn = getattr(lib, name)
+                    fn.argtypes, fn.restype = argtypes, c_int
+                for name, (res, argtypes) in PLAIN.items():
+                    fn = getattr(lib, name)
+                    fn.argtypes, fn.restype = argtypes, res
+            except AttributeError as e:  # entry points added without a version bump (nova_pointset_assignment*)
+                raise NovaHipError(f"{_LIB_PATH} lacks an entry point this package binds ({e}): rebuild it with "
+                                   "`make -C nova_pointcloud_amd/csrc`") from e
             _lib = lib
         if check_device and not _device_ok:
             if not torch.cuda.is_available():

@@ -6,8 +6,10 @@ Same function names, arguments and results as the reference's evaluation code
   GlobalNormalizer                                           test_optimize.py:32-77
   np.save of each generated point cloud                      README.md:108-113
 with the O(N M) distance work (torch.cdist + min, the assignment cost matrix) in libnova_hip.so
-(csrc/pointset.hip). The optimal assignment itself is scipy's linear_sum_assignment on the host, exactly as in the
-reference. GPU tensors only: there is no CPU path here (NovaHipError for CPU tensors or a missing library).
+(csrc/pointset.hip). The optimal assignment itself is scipy's linear_sum_assignment on the host by default, exactly as in
+the reference; assignment="device" solves it on the GPU instead (optimal_assignment, csrc/assign.hip: an integer auction
+whose mean matched distance is within 2^-18 of the optimum). GPU tensors only: there is no CPU path here (NovaHipError
+for CPU tensors or a missing library).
 
 Set-level quality of a generated set against a reference set (MMD, COV, 1-NNA under the Chamfer distance, the numbers
 of PointFlow and its successors): chamfer_matrix (csrc/chamfer.hip), distribution_metrics_from_matrices,
@@ -23,6 +25,9 @@ how the clouds are normalised: normalize_clouds puts each cloud into that ball o
 
 Bringing sets to the point count those metrics need (generated clouds have 2048 points, published reference shapes are
 stored denser, and the EMD takes equal counts of at most 4096): farthest_point_sample (csrc/fps.hip) and resample_clouds.
+
+The exact EMD on the GPU: optimal_assignment (csrc/assign.hip), and assignment="device" of compute_emd_distance, emd_approx
+and robust_emd.
 """
 import json
 import math
@@ -90,10 +95,25 @@ def _assignment_mean(cost):
     return cost[rows, cols].mean()
 
 
-def compute_emd_distance(pred, target):
+ASSIGNMENT_MODES = ("host", "device")
+
+
+def _assignment_mode(assignment):
+    if assignment not in ASSIGNMENT_MODES:
+        raise ValueError(f"assignment must be one of {ASSIGNMENT_MODES}, got {assignment!r}")
+    return assignment == "device"
+
+
+def compute_emd_distance(pred, target, assignment="host"):
     """Earth mover's distance by optimal assignment (test_optimize.py:385-415): clamp +-5, equal point counts, mean
-    matched distance per sample (scipy linear_sum_assignment on the host, as in the reference), batch mean in [0, 10]."""
+    matched distance per sample, batch mean in [0, 10]. assignment="host" (the default) is scipy linear_sum_assignment on
+    the host, as in the reference; "device" is optimal_assignment on the GPU with the same clamp (no cost matrix, no copy;
+    each sample's mean within ASSIGN_QUANTUM = 2^-18 of the host's)."""
+    device = _assignment_mode(assignment)
     n = min(pred.shape[1], target.shape[1])
+    if device:
+        emd = optimal_assignment(pred[:, :n], target[:, :n], clamp=5.0)[1]
+        return emd.mean().clamp(0.0, 10.0)
     cost = pairwise_dist(pred[:, :n], target[:, :n], 5.0).cpu().numpy()
     emd = torch.tensor([float(_assignment_mean(c)) for c in cost], dtype=torch.float32, device=pred.device)
     return emd.mean().clamp(0.0, 10.0)
@@ -109,9 +129,18 @@ def distChamfer(a, b):
     return through_log(nn_dist(a, b, 1.0, unit_norm=True)), through_log(nn_dist(b, a, 1.0, unit_norm=True))
 
 
-def emd_approx(x, y):
-    """Per-sample EMD of train_newloss.py:352-372 (clamp +-2, distances floored at 1e-8): tensor [B]."""
+def emd_approx(x, y, assignment="host"):
+    """Per-sample EMD of train_newloss.py:352-372 (clamp +-2, distances floored at 1e-8): tensor [B]. assignment="host"
+    (the default) is scipy on the host, as in the reference; "device" is optimal_assignment on the GPU with the same
+    clamp. There the floor of 1e-8 is applied to the matched per-row distances AFTER the assignment, where the reference
+    floors the cost matrix BEFORE it: a floored matrix differs from the plain one by at most 1e-8 per entry, so the two
+    means can differ only by that same 1e-8 per point (on top of the 2^-18 of the assignment itself)."""
     assert x.size(1) == y.size(1), "EMD only works if two point clouds are equal size"
+    if _assignment_mode(assignment):
+        idx = optimal_assignment(x, y, clamp=2.0)[0]
+        xc, yc = _points(x, "x").clamp(-2.0, 2.0), _points(y, "y").clamp(-2.0, 2.0)
+        matched = torch.gather(yc, 1, idx[:, :, None].expand(-1, -1, 3))
+        return (xc - matched).square().sum(dim=-1).sqrt().clamp_min(1e-8).mean(dim=1).to(x)
     cost = np.maximum(pairwise_dist(x, y, 2.0).cpu().numpy(), 1e-8)
     return torch.from_numpy(np.stack([_assignment_mean(c) for c in cost]).reshape(-1)).to(x)
 
@@ -121,8 +150,113 @@ def robust_chamfer_distance(pred, gt):
     return (dl.mean() + dr.mean()) / 2
 
 
-def robust_emd(pred, gt):
-    return emd_approx(pred, gt).mean()
+def robust_emd(pred, gt, assignment="host"):
+    return emd_approx(pred, gt, assignment=assignment).mean()
+
+
+# ----------------------------------------------------------------------------------------------------
+# the optimal assignment itself on the GPU
+# ----------------------------------------------------------------------------------------------------
+ASSIGN_MAX_POINTS = 4096  # == NOVA_ASSIGN_MAX_POINTS of include/nova_hip.h
+ASSIGN_QUANTUM = 2.0 ** -18  # the cost quantum of the integer scheme (include/nova_hip.h, nova_pointset_assignment)
+# (row, column) cost evaluations of one bidding wave per launch. A bidding row visits its n columns 64 at a time at ~45 vector
+# issues a visit; late in an auction one row bids per round, so a round is ~n / 64 x 45 issues of one latency-bound wave plus
+# three barriers, ~2.5 ns per column: 2^22 visits are ~10 ms, and the few early rounds in which every row bids (n / 16 times
+# the work, spread over 16 waves) bring a launch to a few tens. Sized from that instruction count, NOT yet from a measured
+# round time: tools/assignment_bench.py writes profiles/assignment_bench.json, and this constant is to be re-derived from its
+# longest single launch (optimal assignment)
+_ASSIGN_COLUMN_VISITS_PER_LAUNCH = 1 << 22
+
+
+def assignment_kernel_shape(n_points):
+    """(workgroup size T, capacity NP) csrc/assign.hip runs a pair of `n_points`-point clouds with."""
+    for limit, shape in ((64, (64, 64)), (256, (256, 256)), (1024, (256, 1024)), (2048, (512, 2048)), (ASSIGN_MAX_POINTS, (1024, 4096))):
+        if n_points <= limit:
+            return shape
+    raise ValueError(f"the assignment kernel takes 1 .. {ASSIGN_MAX_POINTS} points per cloud, got {n_points}")
+
+
+def _positive_int(v, name):
+    if not isinstance(v, int) or isinstance(v, bool) or v < 1:
+        raise ValueError(f"{name} must be a positive integer, got {v!r}")
+    return v
+
+
+def _assignment_arguments(x, y, clamp, max_rounds, rounds_per_launch):
+    """ValueError for everything about the arguments that does not need the GPU (checked before the device, so it holds
+    for CPU tensors too). Returns (max_rounds, rounds_per_launch) with the defaults filled in."""
+    for t, name in ((x, "x"), (y, "y")):
+        if not torch.is_tensor(t):
+            raise ValueError(f"{name}: expected a tensor [B, n, 3], got {type(t).__name__}")
+        if t.dim() != 3 or t.shape[-1] != 3:
+            raise ValueError(f"{name}: expected [B, n, 3] points, got {tuple(t.shape)}")
+    if x.shape[0] != y.shape[0]:
+        raise ValueError(f"x holds {x.shape[0]} clouds, y {y.shape[0]}: the assignment pairs x[b] with y[b]")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"the assignment needs equal point counts (got {x.shape[1]} (x) and {y.shape[1]} (y))")
+    n = x.shape[1]
+    if not 1 <= n <= ASSIGN_MAX_POINTS:
+        raise ValueError(f"the assignment kernel takes 1 .. {ASSIGN_MAX_POINTS} points per cloud, got {n}")
+    if clamp is not None and not (isinstance(clamp, (int, float)) and not isinstance(clamp, bool) and 0 < clamp < math.inf):
+        raise ValueError(f"clamp must be None or a positive finite number, got {clamp!r}")
+    max_rounds = 64 * n + 1024 if max_rounds is None else _positive_int(max_rounds, "max_rounds")
+    rounds_per_launch = (max(16, _ASSIGN_COLUMN_VISITS_PER_LAUNCH // n) if rounds_per_launch is None
+                         else _positive_int(rounds_per_launch, "rounds_per_launch"))
+    if x.device != y.device:
+        raise ValueError(f"x is on {x.device}, y on {y.device}")
+    for t, name in ((x, "x"), (y, "y")):
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError(f"{name}: points must be finite")
+    return max_rounds, rounds_per_launch
+
+
+def optimal_assignment(x, y, clamp=None, max_rounds=None, rounds_per_launch=None, return_rounds=False):
+    """The optimal assignment between the clouds x [B, n, 3] and y [B, n, 3] on the GPU, pair by pair (1 <= n <= 4096):
+    (index int64 [B, n], cost float32 [B]) on the input's device. index[b] is the permutation that matches x[b, i] to
+    y[b, index[b, i]] with the smallest mean Euclidean distance, cost[b] that mean in float32. `clamp` (None: off) clamps
+    every coordinate to [-clamp, clamp] first, as pairwise_dist does. This is what scipy's linear_sum_assignment gives on
+    the pairwise_dist matrix, up to the cost quantum: costs are rounded to multiples of ASSIGN_QUANTUM = 2^-18 and that
+    integer problem is solved exactly (a Jacobi auction with epsilon scaling; the scheme is spelled out in
+    include/nova_hip.h at nova_pointset_assignment, the kernel is csrc/assign.hip), so the mean is within 2^-18 of the
+    optimal mean, and where several assignments are that close any of them may come back. The result depends on the pair
+    alone: bitwise the same for every batch, every rounds_per_launch and every run.
+
+    The auction runs in launches of `rounds_per_launch` bidding rounds (default: _ASSIGN_COLUMN_VISITS_PER_LAUNCH / n)
+    until every pair is done. `max_rounds` (default 64 n + 1024, more than ten times what random clouds need) caps the
+    rounds of a pair: when it is used up, NovaHipError names the unfinished pairs; the call never loops on. NovaHipError
+    also for a pair whose clamped bounding box has a diagonal of 4096 or more (the integer range of the kernel).
+    return_rounds=True adds a third result, int64 [B]: the bidding rounds every pair took."""
+    max_rounds, per_launch = _assignment_arguments(x, y, clamp, max_rounds, rounds_per_launch)
+    x, y = _points(x, "x"), _points(y, "y")
+    B, n = x.shape[0], x.shape[1]
+    idx = torch.empty(B, n, dtype=torch.int32, device=x.device)
+    cost = torch.empty(B, dtype=torch.float32, device=x.device)
+    rounds = torch.zeros(B, dtype=torch.int32, device=x.device)
+    if B > 0:
+        lo, hi = (-float(clamp), float(clamp)) if clamp is not None else (0.0, 0.0)
+        with torch.cuda.device(x.device):
+            stride = int(hip.load().nova_pointset_assignment_state_bytes(n))
+            state = torch.empty(B * stride, dtype=torch.uint8, device=x.device)
+            flag = torch.zeros(1, dtype=torch.int32, device=x.device)
+            stream, left, restart = hip.stream_ptr(), max_rounds, 1
+            while True:
+                step = min(per_launch, left)
+                hip.call("nova_pointset_assignment", x.data_ptr(), y.data_ptr(), idx.data_ptr(), cost.data_ptr(), state.data_ptr(),
+                         B, n, lo, hi, 0 if clamp is None else 1, step, restart, flag.data_ptr(), stream)
+                left, restart = left - step, 0
+                status = int(flag)
+                if status == 1:
+                    break
+                if status < 0:
+                    bad = torch.nonzero(cost == -2.0).flatten().tolist()
+                    raise hip.NovaHipError(f"optimal_assignment: pair(s) {bad} outside the kernel's integer range (bounding-box "
+                                           "diagonal >= 4096 or a bid >= 2^49); scale the clouds down")
+                if left == 0:
+                    bad = torch.nonzero(cost < 0).flatten().tolist()
+                    raise hip.NovaHipError(f"optimal_assignment: pair(s) {bad} not finished after max_rounds = {max_rounds} bidding rounds")
+            if return_rounds:
+                hip.call("nova_pointset_assignment_rounds", state.data_ptr(), rounds.data_ptr(), B, n, stream)
+    return (idx.long(), cost, rounds.long()) if return_rounds else (idx.long(), cost)
 
 
 # ----------------------------------------------------------------------------------------------------
