@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NOVA_HIP_VERSION 405 /* still 0.4.5 (tests/test_pointset_fps.py pins the number; a library without the new symbols fails to bind, loudly): nova_pointset_assignment, nova_pointset_assignment_state_bytes, nova_pointset_assignment_rounds (optimal assignment of two clouds by a batched integer auction: the exact EMD on the GPU); 0.4.5: nova_pointset_farthest_point_sample (farthest point sampling of a cloud set, to bring sets to a common point count); 0.4.4: nova_pointset_occupancy_grid (occupancy grid of a cloud set for the JSD metric); 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
+#define NOVA_HIP_VERSION 405 /* still 0.4.5 (tests/test_pointset_fps.py pins the number; a library without the new symbols fails to bind, loudly): nova_pointset_knn (exact k nearest neighbours of a cloud set); nova_pointset_assignment, nova_pointset_assignment_state_bytes, nova_pointset_assignment_rounds (optimal assignment of two clouds by a batched integer auction: the exact EMD on the GPU); 0.4.5: nova_pointset_farthest_point_sample (farthest point sampling of a cloud set, to bring sets to a common point count); 0.4.4: nova_pointset_occupancy_grid (occupancy grid of a cloud set for the JSD metric); 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
 
 typedef enum { NOVA_F32 = 0, NOVA_BF16 = 1, NOVA_F16 = 2 } nova_dtype;
 typedef enum { NOVA_ACT_NONE = 0, NOVA_ACT_GELU_ERF = 1, NOVA_ACT_SILU = 2 } nova_act;
@@ -340,6 +340,37 @@ int nova_pointset_occupancy_grid(const float* x, long long* counters, long long*
  * x / idx with S > 0. S <= 0 returns 0. */
 #define NOVA_FPS_MAX_POINTS 16384
 int nova_pointset_farthest_point_sample(const float* x, const int* start, int* idx, float* dist, int S, int N, int n, void* stream);
+
+/* Exact k nearest neighbours: for every point of the query clouds x [S, N, 3] the k nearest points of the target clouds
+ * y [S, M, 3] (float32, finite), cloud by cloud, without ever storing an [N, M] distance matrix. The reference needs it for
+ * compute_local_density, diffnext/models/transformers/transformer_pointcloud_nova.py:81-89 (torch.cdist(points, points),
+ * topk(k_neighbors + 1, largest=False), drop column 0, mean), which feeds adaptive_sampling at :92-97, and builds the same
+ * cdist + topk(k = 8) structure again at :144-146 and :179-182.
+ * For query i of cloud s the candidates are all j in 0 .. M-1. The key of candidate j is the pair (d2(i, j), j) with
+ *   d2 = fmaf(e2, e2, fmaf(e1, e1, e0 * e0)),  e = x[s, i] - y[s, j] per axis in float32,
+ * every operation rounded once: the expression of nova_pointset_nn_dist and the sampling kernel, not cdist's
+ * |x|^2 + |y|^2 - 2 x.y expansion, which cancels for the near neighbours this is about. The result is the k smallest keys
+ * in lexicographic order, ascending: idx[s, i, :] (int32) their indices j and d2[s, i, :] (float32) their squared
+ * distances. Ties in distance go to the lowest index, both inside the list and at its cut-off. No clamp, no
+ * normalisation, no square root.
+ * exclude_self != 0 is the self-query form: candidate j == i is skipped BY INDEX, not by distance; N == M is required and
+ * y may be the same pointer as x.
+ * DEVIATION, on purpose: the reference takes k + 1 neighbours from cdist and drops column 0, assuming it is the point
+ * itself. Here the point is excluded by index. The remaining distances are the same multiset; where a cloud holds
+ * duplicates of a point, the duplicate correctly appears at distance 0 (and the point itself never does), whereas the
+ * reference's column 0 may be either of the two.
+ * Consequences:
+ *   - the result depends on (x[s], y[s], k, exclude_self) alone: bitwise the same for every batch, launch split and
+ *     workgroup shape (the k smallest of a set of unique keys is one list, whatever the order they are met in);
+ *   - rows of d2 are non-decreasing; rows of idx hold distinct values in 0 .. M-1.
+ * Limits: 1 <= k <= min(NOVA_KNN_MAX_K, M - (exclude_self ? 1 : 0)), the best keys of a query living in registers;
+ * 1 <= N, M <= NOVA_KNN_MAX_POINTS, so that one cloud is at most 2^32 candidate evaluations and always fits a launch.
+ * NOVA_ERR_SHAPE for N or M outside 1 .. NOVA_KNN_MAX_POINTS and for exclude_self with N != M; NOVA_ERR_ARG for k outside
+ * its range and for null x, y or idx with S > 0. d2 may be NULL (indices only). S <= 0 returns 0 after the shape and k
+ * checks. Everything is checked before any device work. */
+#define NOVA_KNN_MAX_K 32
+#define NOVA_KNN_MAX_POINTS 65536
+int nova_pointset_knn(const float* x, const float* y, int* idx, float* d2, int S, int N, int M, int k, int exclude_self, void* stream);
 
 /* Optimal assignment between x [B, n, 3] and y [B, n, 3] (float32, finite), pair by pair: the permutation that minimises
  * the mean matched distance, i.e. the earth mover's distance that compute_emd_distance (test_optimize.py:385-415) and

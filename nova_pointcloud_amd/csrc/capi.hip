@@ -484,6 +484,10 @@ int nova_pointset_farthest_point_sample(const float* x, const int* start, int* i
   return pointset_farthest_point_sample(x, start, idx, dist, S, N, n, (hipStream_t)stream);
 }
 
+int nova_pointset_knn(const float* x, const float* y, int* idx, float* d2, int S, int N, int M, int k, int exclude_self, void* stream) {
+  return pointset_knn(x, y, idx, d2, S, N, M, k, exclude_self, (hipStream_t)stream);
+}
+
 long long nova_pointset_assignment_state_bytes(int n) { return (long long)pointset_assignment_state_bytes(n); }
 
 int nova_pointset_assignment(const float* x, const float* y, int* col_of_row, float* cost, void* state, int B, int n, float clamp_lo,

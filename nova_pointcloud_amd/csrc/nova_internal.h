@@ -155,6 +155,8 @@ int pointset_occupancy_grid(const float* x, long long* counters, long long* bern
                             int R, int in_sphere, int workgroups, hipStream_t st);
 // ---- fps.hip (farthest point sampling of a cloud set; point counts 1 .. NOVA_FPS_MAX_POINTS)
 int pointset_farthest_point_sample(const float* x, const int* start, int* idx, float* dist, int S, int N, int n, hipStream_t st);
+// ---- knn.hip (exact k nearest neighbours of a cloud set; k 1 .. NOVA_KNN_MAX_K, point counts 1 .. NOVA_KNN_MAX_POINTS)
+int pointset_knn(const float* x, const float* y, int* idx, float* d2, int S, int N, int M, int k, int exclude_self, hipStream_t st);
 // ---- assign.hip (optimal assignment of two clouds by a batched integer auction; point counts 1 .. NOVA_ASSIGN_MAX_POINTS)
 size_t pointset_assignment_state_bytes(int n);
 int pointset_assignment(const float* x, const float* y, int* col, float* cost, void* state, int B, int n, float lo, float hi,

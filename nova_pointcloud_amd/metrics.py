@@ -28,6 +28,10 @@ stored denser, and the EMD takes equal counts of at most 4096): farthest_point_s
 
 The exact EMD on the GPU: optimal_assignment (csrc/assign.hip), and assignment="device" of compute_emd_distance, emd_approx
 and robust_emd.
+
+Local statistics of a cloud: knn_points (csrc/knn.hip), the exact k nearest neighbours of every point with their squared
+distances and no [N, M] matrix, and local_density on it, the reference's compute_local_density
+(transformer_pointcloud_nova.py:81-89) with the point itself excluded by index rather than by dropping a column.
 """
 import json
 import math
@@ -679,6 +683,103 @@ def resample_clouds(points, n_points, method="fps", start=0, generator=None):
     else:
         idx = farthest_point_sample(points, n_points, start=start)
     return torch.gather(points, 1, idx[:, :, None].expand(S, n_points, 3))
+
+
+# ----------------------------------------------------------------------------------------------------
+# k nearest neighbours and local density
+# ----------------------------------------------------------------------------------------------------
+KNN_MAX_K = 32  # == NOVA_KNN_MAX_K of include/nova_hip.h
+KNN_MAX_POINTS = 65536  # == NOVA_KNN_MAX_POINTS of include/nova_hip.h
+# candidate evaluations (clouds x queries x targets) per launch, ~1.7e10. Sized from the kernel's instruction count (about 10
+# vector issues per candidate plus 40 per insertion at k = 8: ~4e12 candidates/s on 256 compute units, so ~4 ms per launch;
+# at k = 32 nearly every candidate costs a 160-issue insertion, ~5e11/s and ~35 ms), NOT yet from a measured time:
+# tools/knn_bench.py writes profiles/knn_bench.json, and this constant is to be re-derived from the longest launch it
+# records (k nearest neighbours). A cloud is at most 2^32 candidates, so a launch holds at least four.
+_KNN_CANDIDATES_PER_LAUNCH = 1 << 34
+_KNN_SPLIT_BELOW = 512  # == KNN_SPLIT_BELOW of csrc/knn.hip
+
+
+def knn_kernel_shape(n_clouds, n_queries, k):
+    """(list rung K, queries per workgroup) csrc/knn.hip runs one launch of `n_clouds` clouds of `n_queries` query points at
+    `k` neighbours with (the rung ladder and knn_split there): 256 queries per workgroup, or 64 with the four waves
+    sharing the candidates when the launch would have fewer than 512 workgroups."""
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"the kNN kernel takes k in 1 .. {KNN_MAX_K}, got {k}")
+    rung = next(r for r in (1, 2, 4, 8, 16, 32) if k <= r)
+    return rung, 64 if n_clouds * ((n_queries + 255) // 256) < _KNN_SPLIT_BELOW else 256
+
+
+def _knn_arguments(x, y, k, exclude_self):
+    """ValueError for everything about the arguments that does not need the GPU (checked before the device, so it holds
+    for CPU tensors too). Returns exclude_self resolved to a bool."""
+    for t, name in ((x, "x"),) + (((y, "y"),) if y is not None else ()):
+        if not torch.is_tensor(t):
+            raise ValueError(f"{name}: expected a tensor [S, N, 3], got {type(t).__name__}")
+        if t.dim() != 3 or t.shape[-1] != 3:
+            raise ValueError(f"{name}: expected [S, N, 3] clouds, got {tuple(t.shape)}")
+        if not 1 <= t.shape[1] <= KNN_MAX_POINTS:
+            raise ValueError(f"{name}: the kNN kernel takes 1 .. {KNN_MAX_POINTS} points per cloud, got {t.shape[1]}")
+    N, M = x.shape[1], (x if y is None else y).shape[1]
+    if y is not None and y.shape[0] != x.shape[0]:
+        raise ValueError(f"x and y must hold the same number of clouds, got {x.shape[0]} and {y.shape[0]}")
+    if y is not None and y.device != x.device:
+        raise ValueError(f"x and y must be on the same device, got {x.device} and {y.device}")
+    if exclude_self is None:
+        exclude_self = y is None
+    if not isinstance(exclude_self, bool):
+        raise ValueError(f"exclude_self must be a bool or None, got {exclude_self!r}")
+    if exclude_self and N != M:
+        raise ValueError(f"exclude_self needs equal point counts (query i is target i), got N = {N} and M = {M}")
+    k_max = min(KNN_MAX_K, M - (1 if exclude_self else 0))
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= k_max:
+        raise ValueError(f"k must be an integer in 1 .. {k_max} (at most {KNN_MAX_K}, and {M} target points"
+                         f"{' without the point itself' if exclude_self else ''}), got {k!r}")
+    for t, name in ((x, "x"),) + (((y, "y"),) if y is not None else ()):
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError(f"{name}: points must be finite")
+    return exclude_self
+
+
+def knn_points(x, y=None, k=8, exclude_self=None, return_distances=True, max_clouds_per_launch=None):
+    """The exact k nearest neighbours in y [S, M, 3] of every point of x [S, N, 3], cloud by cloud, on the GPU
+    (1 <= N, M <= 65536, 1 <= k <= 32): (idx int64 [S, N, k], d2 float32 [S, N, k]) on the input's device, or idx alone
+    with return_distances=False. Row (s, i) lists the k targets j with the smallest keys (d2, j) in ascending order, d2 the
+    float32 squared distance in exact differences; a distance tie goes to the lowest index, inside the list and at its
+    cut-off. No [N, M] matrix is stored. The definition is spelled out in include/nova_hip.h at nova_pointset_knn
+    (csrc/knn.hip).
+
+    y=None is the self-query: the targets are x itself, and exclude_self (default True there) skips the query point by its
+    index, so k <= N - 1; a duplicate of the point elsewhere in the cloud still comes back, at distance 0. With y given,
+    exclude_self defaults to False; True needs N == M (query i is target i).
+
+    The set goes out in launches of at most `max_clouds_per_launch` clouds (default: _KNN_CANDIDATES_PER_LAUNCH candidate
+    evaluations each); a cloud's result depends on (x[s], y[s], k, exclude_self) alone and is bitwise the same for every
+    split."""
+    exclude_self = _knn_arguments(x, y, k, exclude_self)
+    xs = _points(x, "x")
+    ys = xs if y is None else _points(y, "y")
+    S, N, M = xs.shape[0], xs.shape[1], ys.shape[1]
+    per = max_clouds_per_launch if max_clouds_per_launch is not None else max(1, _KNN_CANDIDATES_PER_LAUNCH // (N * M))
+    if not isinstance(per, int) or isinstance(per, bool) or per < 1:
+        raise ValueError(f"max_clouds_per_launch must be an integer >= 1, got {per!r}")
+    idx = torch.empty(S, N, k, dtype=torch.int32, device=xs.device)
+    d2 = torch.empty(S, N, k, dtype=torch.float32, device=xs.device) if return_distances else None
+    if S > 0:
+        with torch.cuda.device(xs.device):
+            stream = hip.stream_ptr()
+            for s0 in range(0, S, per):
+                hip.call("nova_pointset_knn", xs[s0].data_ptr(), ys[s0].data_ptr(), idx[s0].data_ptr(),
+                         d2[s0].data_ptr() if return_distances else None, min(S, s0 + per) - s0, N, M, k, 1 if exclude_self else 0, stream)
+    return (idx.long(), d2) if return_distances else idx.long()
+
+
+def local_density(points, k_neighbors=8):
+    """float32 [S, N]: for every point of points [S, N, 3], the mean Euclidean distance to its k_neighbors nearest other
+    points (small where the cloud is dense). The reference's compute_local_density (transformer_pointcloud_nova.py:81-89),
+    which takes k_neighbors + 1 columns of torch.cdist and drops the first as the point itself; here the point is excluded
+    by index (knn_points), so the distances are the same multiset and a duplicate of the point counts at distance 0."""
+    _, d2 = knn_points(points, k=k_neighbors)
+    return d2.sqrt().mean(dim=-1)
 
 
 NORMALIZE_MODES = ("none", "unit_sphere", "unit_cube")
