@@ -37,8 +37,8 @@
 //
 // Capacity forms by point count (assign_config below), workgroup size T and capacity NP:
 //   n <= 64: 64 / 64 (one wave)   <= 256: 256 / 256   <= 1024: 256 / 1024   <= 2048: 512 / 2048   <= 4096: 1024 / 4096
-#include "common.h"
 #include "nova_internal.h"
+#include "pointset_common.h"
 
 namespace nova {
 
@@ -74,18 +74,15 @@ template <int NP> struct AssignShared {
   int err;
 };
 
+// a 64-bit key moved as its two halves
 template <int CTRL> __device__ __forceinline__ uint64_t assign_dpp(uint64_t v) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, 0xf, 0xf, true);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, 0xf, 0xf, true);
+  const uint32_t lo = dpp_move<CTRL>((uint32_t)v), hi = dpp_move<CTRL>((uint32_t)(v >> 32));
   return (uint64_t)hi << 32 | lo;
 }
-__device__ __forceinline__ uint64_t assign_min(uint64_t a, uint64_t b) { return a < b ? a : b; }
-__device__ __forceinline__ uint64_t assign_max(uint64_t a, uint64_t b) { return a > b ? a : b; }
-
 // the two smallest of the union of two pairs (m1 < m2 within a pair; all keys distinct except the ASSIGN_NONE padding)
 __device__ __forceinline__ void assign_merge(uint64_t& m1, uint64_t& m2, uint64_t p1, uint64_t p2) {
-  const uint64_t lo = assign_min(m1, p1), hi = assign_max(m1, p1);
-  m2 = assign_min(hi, assign_min(m2, p2));
+  const uint64_t lo = umin(m1, p1), hi = umax(m1, p1);
+  m2 = umin(hi, umin(m2, p2));
   m1 = lo;
 }
 template <int CTRL> __device__ __forceinline__ void assign_merge_dpp(uint64_t& m1, uint64_t& m2) {
@@ -108,7 +105,7 @@ template <bool HALVES> __device__ __forceinline__ void assign_merge_swap(uint64_
   m2 = a2;
   assign_merge(m1, m2, b1, b2);
 }
-// every lane ends with the wave's two smallest keys (the pairing of wave_combine)
+// every lane ends with the wave's two smallest keys, on the pairing of wave_combine
 __device__ __forceinline__ void assign_wave_min2(uint64_t& m1, uint64_t& m2) {
   assign_merge_dpp<0x141>(m1, m2);
   assign_merge_dpp<0xb1>(m1, m2);
@@ -118,12 +115,11 @@ __device__ __forceinline__ void assign_wave_min2(uint64_t& m1, uint64_t& m2) {
   assign_merge_swap<true>(m1, m2);
 }
 
-__device__ __forceinline__ float assign_clamp(float v, float lo, float hi, int use) { return use ? fminf(fmaxf(v, lo), hi) : v; }
+__device__ __forceinline__ float assign_clamp(float v, float lo, float hi, int use) { return use ? clampf(v, lo, hi) : v; }
 
-// the float32 cost of the header: the expression of pairwise_dist_kernel (pointset.hip), every operation rounded once
+// the float32 cost of the header, as pairwise_dist_kernel (pointset.hip) computes it: sqdist3 and a correctly rounded square root
 __device__ __forceinline__ float assign_dist(float ax, float ay, float az, float bx, float by, float bz) {
-  const float e0 = ax - bx, e1 = ay - by, e2 = az - bz;
-  return sqrtf(__builtin_fmaf(e2, e2, __builtin_fmaf(e1, e1, __fmul_rn(e0, e0))));
+  return sqrtf(sqdist3(ax, ay, az, bx, by, bz));
 }
 // llrint(c * 2^18): the product is exact (a power of two), rintf rounds to nearest even, and c < 4097 keeps it in int32
 __device__ __forceinline__ int64_t assign_quantise(float c) { return (int64_t)(int)__builtin_rintf(c * (float)(1 << ASSIGN_SCALE_LOG2)); }
@@ -264,8 +260,8 @@ __global__ __launch_bounds__(T) void assign_kernel(const float* __restrict__ x, 
       for (int j = lane; j < n; j += 64) {
         const int64_t c = assign_quantise(assign_dist(px, py, pz, s.yx[j], s.yy[j], s.yz[j])) * n1;
         const uint64_t a = ((uint64_t)c + (s.key[j] >> ASSIGN_ROW_BITS)) << ASSIGN_ROW_BITS | (uint64_t)j;
-        m2 = assign_min(m2, assign_max(m1, a));
-        m1 = assign_min(m1, a);
+        m2 = umin(m2, umax(m1, a));
+        m1 = umin(m1, a);
       }
       assign_wave_min2(m1, m2);
       if (lane == 0) {
@@ -317,8 +313,8 @@ __global__ __launch_bounds__(T) void assign_kernel(const float* __restrict__ x, 
     if (done <= 0) atomicMin(all_done, done);
   }
   if (done == 1) {
-    // the mean matched distance in a fixed order: a thread's rows in index order, the wave on wave_combine's pairing,
-    // the waves in index order, one division
+    // the mean matched distance in a fixed order: a thread's rows in index order, then block_sum_fixed's order (wave_sum's
+    // pairing, the waves in index order) with thread 0 alone reading the slots, one division
     float sum = 0.f;
     for (int i = t; i < NP; i += T) {
       float c = 0.f;

@@ -6,7 +6,7 @@
 // One workgroup owns one cloud pair and writes its entry (and the mirrored entry in symmetric mode): no global atomics,
 // and every sum runs in a fixed order, so an entry is bitwise the same whatever pair grid the host launches.
 //
-// Form: exact differences e = p - q, d = fma(e2, e2, fma(e1, e1, e0 * e0)) on the vector unit. For near points p - q is
+// Form: exact differences e = p - q, d = sqdist3 (pointset_common.h) on the vector unit. For near points p - q is
 // exact (Sterbenz), so d carries a few ulp of relative error whatever the translation of the clouds. The expansion
 // |p|^2 + |q|^2 - 2 p.q (the f32 MFMA could take the dot products) loses ~1e-7 |p|^2 / d^2 per term: with 2048 points on
 // the unit sphere (nearest-neighbour d^2 ~ 6e-3) that is ~2e-5 per term centred and ~3e-3 after a shift by (8, -8, 8).
@@ -21,8 +21,8 @@
 // Roles: P = x when N <= CM_XC, else P = y when M <= CM_XC (both fused); when both clouds exceed CM_XC the workgroup
 // runs the row pass twice, once per direction. Ragged sizes are padded: P with +1e18, Q with -1e18 (finite
 // squares ~1e37 that never win a minimum against points of magnitude << 1e18), and padded entries are not summed.
-#include "common.h"
 #include "nova_internal.h"
+#include "pointset_common.h"
 
 namespace nova {
 
@@ -31,36 +31,12 @@ constexpr int CM_R = 8;                       // register-side points per lane
 constexpr int CM_XC = CM_THREADS * CM_R;      // register-side points per pass
 constexpr int CM_TQ = 1024;                   // streamed points per LDS tile (16 KiB of float4 + 4 KiB of minima)
 constexpr float CM_PAD = 1e18f;
-constexpr uint32_t CM_INF = 0x7f800000u;      // +inf bits
 
 struct CmShared {
   float4 q[CM_TQ];
   uint32_t colmin[CM_TQ];
   float red[CM_THREADS / 64];
 };
-
-__device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
-
-template <int CTRL> __device__ __forceinline__ uint32_t dpp_u(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
-}
-
-__device__ __forceinline__ uint32_t sqdist_bits(float px, float py, float pz, float4 q) {
-  const float e0 = px - q.x, e1 = py - q.y, e2 = pz - q.z;
-  return __float_as_uint(__builtin_fmaf(e2, e2, __builtin_fmaf(e1, e1, __fmul_rn(e0, e0))));
-}
-
-// Workgroup sum in a fixed order (wave_sum's fixed pairing, then the waves in index order); every thread gets it.
-__device__ __forceinline__ float block_sum(float v, CmShared& s) {
-  v = wave_sum(v);
-  __syncthreads();  // earlier readers of s.red are done
-  if ((threadIdx.x & 63) == 0) s.red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float t = s.red[0];
-#pragma unroll
-  for (int w = 1; w < CM_THREADS / 64; ++w) t += s.red[w];
-  return t;
-}
 
 // rsum = sum over p in P of min_{q in Q} |p - q|^2; with COLS (requires nP <= CM_XC) also
 // csum = sum over q in Q of min_{p in P} |p - q|^2. Both are workgroup-uniform on return.
@@ -79,7 +55,7 @@ __device__ void cm_sweep(const float* __restrict__ P, int nP, const float* __res
       px[r] = ok ? P[(size_t)i * 3] : CM_PAD;
       py[r] = ok ? P[(size_t)i * 3 + 1] : CM_PAD;
       pz[r] = ok ? P[(size_t)i * 3 + 2] : CM_PAD;
-      rmin[r] = CM_INF;
+      rmin[r] = F32_INF_BITS;
     }
     for (int q0 = 0; q0 < nQ; q0 += CM_TQ) {
       const int cnt = min(CM_TQ, nQ - q0), cnt4 = (cnt + 3) & ~3;
@@ -87,7 +63,7 @@ __device__ void cm_sweep(const float* __restrict__ P, int nP, const float* __res
       for (int j = t; j < cnt4; j += CM_THREADS) {
         const float* src = Q + (size_t)(q0 + j) * 3;
         s.q[j] = j < cnt ? make_float4(src[0], src[1], src[2], 0.f) : make_float4(-CM_PAD, -CM_PAD, -CM_PAD, 0.f);
-        if (COLS) s.colmin[j] = CM_INF;
+        if (COLS) s.colmin[j] = F32_INF_BITS;
       }
       __syncthreads();
       for (int j = 0; j < cnt4; j += 4) {
@@ -97,7 +73,7 @@ __device__ void cm_sweep(const float* __restrict__ P, int nP, const float* __res
           const float4 q = s.q[j + k];  // same address in every lane: broadcast
 #pragma unroll
           for (int r = 0; r < CM_R; ++r) {
-            const uint32_t d = sqdist_bits(px[r], py[r], pz[r], q);
+            const uint32_t d = __float_as_uint(sqdist3(px[r], py[r], pz[r], q.x, q.y, q.z));
             rmin[r] = umin(rmin[r], d);
             c[k] = r == 0 ? d : umin(c[k], d);
           }
@@ -110,10 +86,7 @@ __device__ void cm_sweep(const float* __restrict__ P, int nP, const float* __res
           // rows: row 0 -> column 0, row 1 -> column 2, row 2 -> column 1, row 3 -> column 3
           const auto rr = __builtin_amdgcn_permlane16_swap(m01, m23, false, false);
           uint32_t m = umin(rr[0], rr[1]);
-          m = umin(m, dpp_u<0x141>(m));  // i <-> 7 - i
-          m = umin(m, dpp_u<0xb1>(m));   // xor 1
-          m = umin(m, dpp_u<0x4e>(m));   // xor 2
-          m = umin(m, dpp_u<0x140>(m));  // i <-> 15 - i
+          m = row_combine(m, [](uint32_t a, uint32_t b) { return umin(a, b); });
           const int row = lane >> 4;
           if ((lane & 15) == 0) atomicMin(&s.colmin[j + (((row & 1) << 1) | (row >> 1))], m);
         }
@@ -127,8 +100,8 @@ __device__ void cm_sweep(const float* __restrict__ P, int nP, const float* __res
     for (int r = 0; r < CM_R; ++r)
       if (p0 + r * CM_THREADS + t < nP) racc += __uint_as_float(rmin[r]);
   }
-  rsum = block_sum(racc, s);
-  csum = COLS ? block_sum(cacc, s) : 0.f;
+  rsum = block_sum_fixed<CM_THREADS / 64>(racc, s.red);
+  csum = COLS ? block_sum_fixed<CM_THREADS / 64>(cacc, s.red) : 0.f;
 }
 
 __global__ __launch_bounds__(CM_THREADS) void chamfer_matrix_kernel(const float* __restrict__ x, const float* __restrict__ y,

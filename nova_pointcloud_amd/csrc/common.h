@@ -106,18 +106,29 @@ template <> struct Half16<f16_t> {
 // and the last two are the gfx950 row swaps. Each step pairs lane groups symmetrically (both partners compute
 // a + b), so all lanes agree bit for bit. Pairing: i <-> 7 - i (row_half_mirror), xor 1, xor 2 (quad_perm),
 // i <-> 15 - i (row_mirror), rows 0|1 and 2|3 (v_permlane16_swap), halves (v_permlane32_swap).
-template <int CTRL> __device__ __forceinline__ float dpp_move(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+// T is any 32-bit value: float, or uint32_t for minima and maxima on bit patterns.
+__device__ __forceinline__ uint32_t bits32(float v) { return __float_as_uint(v); }
+__device__ __forceinline__ uint32_t bits32(uint32_t v) { return v; }
+template <typename T> __device__ __forceinline__ T from_bits32(uint32_t u);
+template <> __device__ __forceinline__ float from_bits32<float>(uint32_t u) { return __uint_as_float(u); }
+template <> __device__ __forceinline__ uint32_t from_bits32<uint32_t>(uint32_t u) { return u; }
+
+template <int CTRL, typename T> __device__ __forceinline__ T dpp_move(T v) {
+  return from_bits32<T>((uint32_t)__builtin_amdgcn_update_dpp(0, (int)bits32(v), CTRL, 0xf, 0xf, true));
 }
-template <typename F> __device__ __forceinline__ float wave_combine(float v, F f) {
+// the four DPP steps: every lane of a row of 16 ends with the row's result
+template <typename T, typename F> __device__ __forceinline__ T row_combine(T v, F f) {
   v = f(v, dpp_move<0x141>(v));
   v = f(v, dpp_move<0xb1>(v));
   v = f(v, dpp_move<0x4e>(v));
-  v = f(v, dpp_move<0x140>(v));
-  const auto r16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  v = f(__uint_as_float(r16[0]), __uint_as_float(r16[1]));
-  const auto r32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-  return f(__uint_as_float(r32[0]), __uint_as_float(r32[1]));
+  return f(v, dpp_move<0x140>(v));
+}
+template <typename T, typename F> __device__ __forceinline__ T wave_combine(T v, F f) {
+  v = row_combine(v, f);
+  const auto r16 = __builtin_amdgcn_permlane16_swap(bits32(v), bits32(v), false, false);
+  v = f(from_bits32<T>(r16[0]), from_bits32<T>(r16[1]));
+  const auto r32 = __builtin_amdgcn_permlane32_swap(bits32(v), bits32(v), false, false);
+  return f(from_bits32<T>(r32[0]), from_bits32<T>(r32[1]));
 }
 __device__ __forceinline__ float wave_sum(float v) { return wave_combine(v, [](float a, float b) { return a + b; }); }
 __device__ __forceinline__ float wave_max(float v) { return wave_combine(v, [](float a, float b) { return fmaxf(a, b); }); }

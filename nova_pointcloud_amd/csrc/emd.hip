@@ -33,8 +33,8 @@
 // weights are known after pass B), so a pair takes 21 sweeps instead of 30, with every sum in its own order.
 // Precision: E = v_exp_f32(level * log2(e) * d2), sqrt = v_sqrt_f32, exact differences p - q as in chamfer.hip (no
 // |p|^2 + |q|^2 - 2 p.q). Padded points (i >= N) carry zero weight and zero mass: their terms are exactly +0.
-#include "common.h"
 #include "nova_internal.h"
+#include "pointset_common.h"
 
 namespace nova {
 
@@ -51,11 +51,6 @@ template <int NP, int WAVES> struct EmdShared {
 // level * log2(e) of level index 0..9 (j = 7 - index): exp(level * d2) = exp2(emd_level_log2(i) * d2)
 __device__ __forceinline__ float emd_level_log2(int i) {
   return i == EMD_LEVELS - 1 ? -0.f : -(float)(1 << (2 * (EMD_LEVELS - 2 - i))) * 0.25f * 1.4426950408889634f;
-}
-
-__device__ __forceinline__ float emd_sqdist(float px, float py, float pz, float4 q) {
-  const float e0 = px - q.x, e1 = py - q.y, e2 = pz - q.z;
-  return __builtin_fmaf(e2, e2, __builtin_fmaf(e1, e1, __fmul_rn(e0, e0)));
 }
 
 // One sweep with the lane's points (R per lane) outside and the n4 points of the other side (Rq) inside, each lane point
@@ -81,7 +76,7 @@ __device__ __forceinline__ void emd_row_sweep(const float4* __restrict__ Rq, con
     for (int u = 0; u < 4; ++u)
 #pragma unroll
       for (int r = 0; r < R; ++r) {
-        const float d2 = emd_sqdist(px[r], py[r], pz[r], q[u]);
+        const float d2 = sqdist3(px[r], py[r], pz[r], q[u].x, q[u].y, q[u].z);
         if (DO_C) {
           const float t = __builtin_amdgcn_exp2f(cC * d2) * q[u].w;
           sw[r] += t;
@@ -162,7 +157,7 @@ __global__ __launch_bounds__(T) void emd_matrix_kernel(const float* __restrict__
     }
   }
 
-  // workgroup sum in a fixed order (wave_sum's fixed pairing, then the waves in index order)
+  // block_sum_fixed's order (wave_sum's pairing, then the waves in index order), with thread 0 alone reading the slots
   cost = wave_sum(cost);
   if ((t & 63) == 0) s.red[t >> 6] = cost;
   __syncthreads();

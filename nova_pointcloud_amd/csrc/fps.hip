@@ -33,39 +33,17 @@
 // workgroup is 4 waves, one per SIMD of a compute unit; more waves add no vector throughput to one cloud, only capacity.
 // The result depends on the cloud and its start index alone (a maximum of unique keys has one value whatever the pairing):
 // it is bitwise the same for every batch, launch split and workgroup shape.
-#include "common.h"
 #include "nova_internal.h"
+#include "pointset_common.h"
 
 namespace nova {
 
 constexpr int FPS_MAX_N = NOVA_FPS_MAX_POINTS;  // include/nova_hip.h
-constexpr uint32_t FPS_INF = 0x7f800000u;       // +inf bits
 
 struct FpsShared {
   u4v a[2][16];  // (mind bits, 0xFFFFFFFF - index, x bits, y bits) of a wave's winner
   float z[2][16];
 };
-
-template <int CTRL> __device__ __forceinline__ uint32_t fps_dpp(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
-}
-__device__ __forceinline__ uint32_t fps_umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
-__device__ __forceinline__ uint32_t fps_umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
-
-// maximum over each row of 16 lanes, every lane of the row ending with it (the first four pairings of wave_combine)
-__device__ __forceinline__ uint32_t fps_row_umax(uint32_t v) {
-  v = fps_umax(v, fps_dpp<0x141>(v));  // i <-> 7 - i
-  v = fps_umax(v, fps_dpp<0xb1>(v));   // xor 1
-  v = fps_umax(v, fps_dpp<0x4e>(v));   // xor 2
-  return fps_umax(v, fps_dpp<0x140>(v));  // i <-> 15 - i
-}
-__device__ __forceinline__ uint32_t fps_wave_umax(uint32_t v) {
-  v = fps_row_umax(v);
-  const auto r16 = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-  v = fps_umax(r16[0], r16[1]);
-  const auto r32 = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-  return fps_umax(r32[0], r32[1]);
-}
 
 __device__ __forceinline__ float fps_readlane(float v, int lane_uniform) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane_uniform));
@@ -92,7 +70,7 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ x, con
     px[r >> 1][r & 1] = ok ? xc[(size_t)i * 3] : 0.f;
     py[r >> 1][r & 1] = ok ? xc[(size_t)i * 3 + 1] : 0.f;
     pz[r >> 1][r & 1] = ok ? xc[(size_t)i * 3 + 2] : 0.f;
-    mind[r] = ok ? FPS_INF : 0u;  // a padded slot stays at 0 under min
+    mind[r] = ok ? F32_INF_BITS : 0u;  // a padded slot stays at 0 under min
   }
   const int s0 = start ? min(max(start[c], 0), N - 1) : 0;  // clamped: an out-of-range start is never dereferenced
   float qx = xc[(size_t)s0 * 3], qy = xc[(size_t)s0 * 3 + 1], qz = xc[(size_t)s0 * 3 + 2];
@@ -100,9 +78,10 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ x, con
   float* dist_c = dist ? dist + c * (size_t)n : nullptr;
   if (t == 0) {
     idx_c[0] = s0;
-    if (dist_c) dist_c[0] = __uint_as_float(FPS_INF);
+    if (dist_c) dist_c[0] = __uint_as_float(F32_INF_BITS);
   }
 
+  const auto mx = [](uint32_t a, uint32_t b) { return umax(a, b); };
   int buf = 0;
   for (int step = 1; step < n; ++step) {
     // 1. update and fold
@@ -111,11 +90,11 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ x, con
 #pragma unroll
     for (int h = 0; h < H; ++h) {
       const f2v e0 = px[h] - q2x, e1 = py[h] - q2y, e2 = pz[h] - q2z;
-      const f2v d = __builtin_elementwise_fma(e2, e2, __builtin_elementwise_fma(e1, e1, e0 * e0));
+      const f2v d = __builtin_elementwise_fma(e2, e2, __builtin_elementwise_fma(e1, e1, e0 * e0));  // sqdist3, element by element
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         const int r = 2 * h + k;
-        mind[r] = fps_umin(mind[r], __float_as_uint(d[k]));
+        mind[r] = umin(mind[r], __float_as_uint(d[k]));
         if (r == 0) {
           bh = mind[0];
         } else if (mind[r] > bh) {  // strict: the lowest slot, i.e. the thread's lowest index, keeps a tie
@@ -127,8 +106,8 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ x, con
     // 2. the wave's maximum key
     const uint32_t mine = br * T + t;
     const uint32_t lo = mine < (uint32_t)N ? 0xFFFFFFFFu - mine : 0u;
-    const uint32_t w_hi = fps_wave_umax(bh);
-    const uint32_t w_lo = fps_wave_umax(bh == w_hi ? lo : 0u);
+    const uint32_t w_hi = wave_combine(bh, mx);
+    const uint32_t w_lo = wave_combine(bh == w_hi ? lo : 0u, mx);
     // the winner's coordinates, in the lane that holds them. w_lo == 0 (a wave of padding only): slot number out of range,
     // nothing selected, and the key 0 written below can never win
     const uint32_t w_idx = 0xFFFFFFFFu - (uint32_t)__builtin_amdgcn_readfirstlane((int)w_lo);
@@ -172,8 +151,8 @@ __global__ __launch_bounds__(T) void fps_kernel(const float* __restrict__ x, con
         a = s.a[buf][k];
         z = s.z[buf][k];
       }
-      const uint32_t r_hi = fps_row_umax(a[0]);
-      const uint32_t r_lo = fps_row_umax(a[0] == r_hi ? a[1] : 0u);
+      const uint32_t r_hi = row_combine(a[0], mx);
+      const uint32_t r_lo = row_combine(a[0] == r_hi ? a[1] : 0u, mx);
       g_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)r_hi);
       g_idx = 0xFFFFFFFFu - (uint32_t)__builtin_amdgcn_readfirstlane((int)r_lo);
       const int g_wave = (int)((g_idx & (T - 1)) >> 6);  // the wave that owns the point: lane g_wave of row 0 read its slot

@@ -36,8 +36,8 @@
 // the test: about 10 vector issues, plus 5 K per insertion. A query sees about K ln(M / K) insertions over a cloud in random
 // order, and a wave pays for one whenever any of its 64 lanes needs it: at k = 8 and M = 15 000 about a quarter of the
 // candidates (some 10 issues each on average), at k = 32 nearly all of them (some 160).
-#include "common.h"
 #include "nova_internal.h"
+#include "pointset_common.h"
 
 namespace nova {
 
@@ -48,9 +48,6 @@ constexpr int KNN_TILE = 1024;        // target points staged per LDS tile (16 K
 constexpr int KNN_CHUNK = 64;         // SPLIT = 4: consecutive tile points one wave takes in turn
 constexpr int KNN_SPLIT_BELOW = 512;  // launches with fewer 256-query workgroups than this run SPLIT = 4
 constexpr uint32_t KNN_EMPTY = 0xFFFFFFFFu;
-
-__device__ __forceinline__ uint32_t knn_umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
-__device__ __forceinline__ uint32_t knn_umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
 
 // (cd, ci) < (d, i); LEX = false compares the distances alone (candidates arriving in ascending index order)
 template <bool LEX> __device__ __forceinline__ bool knn_less(uint32_t cd, int ci, uint32_t d, int i) {
@@ -65,10 +62,10 @@ template <int K, bool LEX> __device__ __forceinline__ void knn_insert(uint32_t (
     const bool up = knn_less<LEX>(cd, ci, d[r - 1], ix[r - 1]);  // the new key goes in front of slot r - 1: r - 1 moves to r
     const bool here = knn_less<LEX>(cd, ci, d[r], ix[r]);
     ix[r] = up ? ix[r - 1] : (here ? ci : ix[r]);
-    d[r] = knn_umax(d[r - 1], knn_umin(cd, d[r]));  // the median, as d[r - 1] <= d[r]
+    d[r] = umax(d[r - 1], umin(cd, d[r]));  // the median, as d[r - 1] <= d[r]
   }
   ix[0] = knn_less<LEX>(cd, ci, d[0], ix[0]) ? ci : ix[0];
-  d[0] = knn_umin(cd, d[0]);
+  d[0] = umin(cd, d[0]);
 }
 
 template <int K, int SPLIT>
@@ -118,8 +115,7 @@ __global__ __launch_bounds__(KNN_T) void knn_kernel(const float* __restrict__ x,
 #pragma unroll 4
       for (int j = b; j < e; ++j) {
         const f4v q = ys[j];
-        const float e0 = x0 - q[0], e1 = x1 - q[1], e2 = x2 - q[2];
-        uint32_t bits = __float_as_uint(fmaf(e2, e2, fmaf(e1, e1, e0 * e0)));
+        uint32_t bits = __float_as_uint(sqdist3(x0, x1, x2, q[0], q[1], q[2]));
         bits = (j0 + j == skip) ? KNN_EMPTY : bits;
         if (bits < d[K - 1]) knn_insert<K, false>(d, ix, bits, j0 + j);
       }

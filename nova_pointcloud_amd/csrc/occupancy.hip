@@ -29,14 +29,14 @@
 //      before the window is cut with floor / ceil, far more than the float32 error of either. For a point just outside
 //      the grid D0 <= |p| - 0.5 + 1.74 h, a window of about 5 x 5 columns; for a point far away it is the whole grid,
 //      R^2 columns, which is the worst case the launch cap of metrics.py is sized by.
-//   3. The candidates are compared by the exact-difference squared distance of chamfer.hip, as a 64-bit key
+//   3. The candidates are compared by the exact-difference squared distance sqdist3, as a 64-bit key
 //      (distance bits << 32 | flat index): the minimum key is the nearest node, ties to the lowest flat index.
 // Slow-path points do not hold up the fast-path lanes of their wave: after the fast-path commit the wave compacts them
 // (ballot + a 64-entry list per wave in LDS) and gives each 64 / m' lanes (m' = the count rounded up to a power of two),
 // which split the point's columns and merge their keys by xor shuffles. One slow point in a wave uses all 64 lanes, 64 slow
 // points use one lane each, and the loop has no cross-lane traffic.
-#include "common.h"
 #include "nova_internal.h"
+#include "pointset_common.h"
 
 namespace nova {
 
@@ -59,11 +59,6 @@ struct OccShared {
   uint32_t outside;
 };
 static_assert(sizeof(OccShared) <= 160 * 1024, "LDS");
-
-__device__ __forceinline__ float occ_sqdist(float px, float py, float pz, float cx, float cy, float cz) {
-  const float e0 = px - cx, e1 = py - cy, e2 = pz - cz;
-  return __builtin_fmaf(e2, e2, __builtin_fmaf(e1, e1, __fmul_rn(e0, e0)));
-}
 
 // clamp(rint((p + 0.5) (R - 1)), 0, R - 1), clamped as a float (any finite p, and NaN -> 0, stay in range)
 __device__ __forceinline__ int occ_round(float p, float rm1) {
@@ -136,8 +131,8 @@ __global__ __launch_bounds__(OCC_THREADS) void occupancy_grid_kernel(const float
       const float sc = r > rin ? rin / r : 1.f;
       int i0 = occ_round(q.x * sc, rm1f), j0 = occ_round(q.y * sc, rm1f), k0 = occ_round(q.z * sc, rm1f);
       if (!occ_member(i0, j0, k0, rm1)) i0 = j0 = k0 = R / 2;  // the centre node (a grid node for every R >= 3)
-      const float d0 = occ_sqdist(q.x, q.y, q.z, s.coord[i0], s.coord[j0], s.coord[k0]);
-      unsigned long long best = ((unsigned long long)__float_as_uint(d0) << 32) | (uint32_t)((i0 * R + j0) * R + k0);
+      const float d0 = sqdist3(q.x, q.y, q.z, s.coord[i0], s.coord[j0], s.coord[k0]);
+      uint64_t best = ((uint64_t)__float_as_uint(d0) << 32) | (uint32_t)((i0 * R + j0) * R + k0);
       const float D0 = sqrtf(d0) * (1.f + 1e-5f) + 1e-6f;
       const int ilo = (int)fminf(fmaxf(floorf((q.x - D0 + 0.5f) * rm1f), 0.f), rm1f);
       const int ihi = (int)fminf(fmaxf(ceilf((q.x + D0 + 0.5f) * rm1f), 0.f), rm1f);
@@ -152,14 +147,14 @@ __global__ __launch_bounds__(OCC_THREADS) void occupancy_grid_kernel(const float
         const int lo = s.klo[ci * R + cj];
         if (lo == 255) continue;
         const int ck = min(max(kr, lo), rm1 - lo);
-        const float d = occ_sqdist(q.x, q.y, q.z, s.coord[ci], s.coord[cj], s.coord[ck]);
-        const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (uint32_t)((ci * R + cj) * R + ck);
-        best = key < best ? key : best;
+        const float d = sqdist3(q.x, q.y, q.z, s.coord[ci], s.coord[cj], s.coord[ck]);
+        const uint64_t key = ((uint64_t)__float_as_uint(d) << 32) | (uint32_t)((ci * R + cj) * R + ck);
+        best = umin(key, best);
       }
       for (int off = g >> 1; off >= 1; off >>= 1) {  // wave-uniform: the g lanes of a point are an aligned group
         const uint32_t hi = __shfl_xor((int)(best >> 32), off), lo = __shfl_xor((int)(uint32_t)best, off);
-        const unsigned long long other = ((unsigned long long)hi << 32) | lo;
-        best = other < best ? other : best;
+        const uint64_t other = ((uint64_t)hi << 32) | lo;
+        best = umin(other, best);
       }
       if (active && sub == 0) occ_commit(s, (int)(uint32_t)best, node, (size_t)c * N + base + __float_as_int(q.w));
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the list is read before the next batch overwrites it

@@ -8,14 +8,12 @@
 // Chamfer is about.
 //   nn_dist        d[b, i] = min_j ||clamp(x[b, i]) - clamp(y[b, j])||     one thread per x point, y tiles through LDS
 //   pairwise_dist  D[b, i, j] = ||clamp(x[b, i]) - clamp(y[b, j])||        the cost matrix of the assignment problem
-#include "common.h"
 #include "nova_internal.h"
+#include "pointset_common.h"
 
 namespace nova {
 
 constexpr int PS_TILE = 1024;  // y points staged per LDS tile (12 KiB)
-
-__device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 
 // unit != 0: points are scaled to unit norm after clamping (distChamfer, train_newloss.py:325-337: x / max(|x|, 1e-8))
 __device__ __forceinline__ void load_point(const float* p, float lo, float hi, int unit, float& a, float& b, float& c) {
@@ -52,8 +50,8 @@ __global__ __launch_bounds__(256) void nn_dist_kernel(const float* __restrict__ 
     }
     __syncthreads();
     for (int j = 0; j < cnt; ++j) {  // every lane reads the same LDS address: broadcast, no conflicts
-      const float e0 = x0 - ys[3 * j], e1 = x1 - ys[3 * j + 1], e2 = x2 - ys[3 * j + 2];
-      best = fminf(best, fmaf(e2, e2, fmaf(e1, e1, e0 * e0)));
+      const float d2 = sqdist3(x0, x1, x2, ys[3 * j], ys[3 * j + 1], ys[3 * j + 2]);
+      best = fminf(best, d2);
     }
   }
   if (i < N) d[(size_t)b * N + i] = sqrtf(best);
@@ -74,8 +72,7 @@ __global__ __launch_bounds__(256) void pairwise_dist_kernel(const float* __restr
     if (i >= N) break;
     float a, bb, c;
     load_point(xb + (size_t)i * 3, lo, hi, 0, a, bb, c);  // wave-uniform address: one scalar-like broadcast load
-    const float e0 = a - y0, e1 = bb - y1, e2 = c - y2;
-    if (j < M) D[((size_t)b * N + i) * M + j] = sqrtf(fmaf(e2, e2, fmaf(e1, e1, e0 * e0)));
+    if (j < M) D[((size_t)b * N + i) * M + j] = sqrtf(sqdist3(a, bb, c, y0, y1, y2));
   }
 }
 

@@ -1,0 +1,41 @@
+// Device helpers shared by the point-set kernels (pointset, chamfer, emd, occupancy, fps, assign, knn): every result of
+// that family is bitwise the same for every batch and launch split, which rests on all of them computing one distance
+// expression and summing in one fixed order. Both are defined here once.
+#pragma once
+#include "common.h"
+
+namespace nova {
+
+constexpr uint32_t F32_INF_BITS = 0x7f800000u;  // +inf; non-negative floats order as their bit patterns
+
+__device__ __forceinline__ uint32_t umin(uint32_t a, uint32_t b) { return a < b ? a : b; }
+__device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
+__device__ __forceinline__ uint64_t umin(uint64_t a, uint64_t b) { return a < b ? a : b; }
+__device__ __forceinline__ uint64_t umax(uint64_t a, uint64_t b) { return a > b ? a : b; }
+
+__device__ __forceinline__ float clampf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
+
+// |p - q|^2 in float32, the expression include/nova_hip.h defines for every point-set entry point: three exact-difference
+// subtractions, one product rounded to float32 and two fused multiply-adds on top of it, in this order. The roundings
+// are WRITTEN OUT (see rope_rotate4 in common.h: left to fp-contract, two kernels inlining the same source line can round
+// differently), so the kNN distances, the Chamfer minima, the assignment's costs and pairwise_dist agree bit for bit.
+__device__ __forceinline__ float sqdist3(float px, float py, float pz, float qx, float qy, float qz) {
+  const float e0 = px - qx, e1 = py - qy, e2 = pz - qz;
+  return __builtin_fmaf(e2, e2, __builtin_fmaf(e1, e1, __fmul_rn(e0, e0)));
+}
+
+// Workgroup sum in a fixed order: wave_sum's pairing inside each wave, then the WAVES waves in index order through one
+// LDS slot each. Every thread gets the sum. Earlier code may still be reading red, so a barrier comes first.
+template <int WAVES> __device__ __forceinline__ float block_sum_fixed(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  const int t = threadIdx.x;
+  if ((t & 63) == 0) red[t >> 6] = v;
+  __syncthreads();
+  float total = red[0];
+#pragma unroll
+  for (int w = 1; w < WAVES; ++w) total += red[w];
+  return total;
+}
+
+}  // namespace nova

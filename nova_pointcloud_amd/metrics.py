@@ -56,6 +56,59 @@ def _points(t, name):
     return t.detach().float().contiguous()
 
 
+def _check_clouds(named, letters="S, n", count_range=None, same_clouds=False, same_points=None, same_device=True, finite=True):
+    """ValueError for everything about the point tensors `named`, a sequence of (tensor, name), that does not need the GPU,
+    in one order, each step over all tensors before the next:
+      1. type        every entry is a tensor
+      2. shape       [<letters>, 3]
+      3. counts      same_clouds: equal cloud counts; same_points (what needs them, for the message): equal point counts;
+                     count_range = (kernel name, maximum): 1 .. maximum points per cloud
+      4. device      same_device: all on one device
+      5. finiteness  finite: no NaN and no infinity
+    _points refuses CPU tensors only after this, so all of it holds for CPU tensors too."""
+    for t, name in named:
+        if not torch.is_tensor(t):
+            raise ValueError(f"{name}: expected a tensor [{letters}, 3], got {type(t).__name__}")
+    for t, name in named:
+        if t.dim() != 3 or t.shape[-1] != 3:
+            raise ValueError(f"{name}: expected [{letters}, 3] clouds, got {tuple(t.shape)}")
+    names = " and ".join(name for _, name in named)
+    if same_clouds and len({t.shape[0] for t, _ in named}) > 1:
+        raise ValueError(f"{names} must hold the same number of clouds, got {' and '.join(str(t.shape[0]) for t, _ in named)}")
+    if same_points and len({t.shape[1] for t, _ in named}) > 1:
+        raise ValueError(f"{same_points} needs equal point counts (got {' and '.join(f'{t.shape[1]} ({name})' for t, name in named)})")
+    if count_range is not None:
+        kernel, most = count_range
+        for t, name in named:
+            if not 1 <= t.shape[1] <= most:
+                raise ValueError(f"{name}: the {kernel} kernel takes 1 .. {most} points per cloud, got {t.shape[1]}")
+    if same_device and len({t.device for t, _ in named}) > 1:
+        raise ValueError(f"{names} must be on the same device, got {' and '.join(str(t.device) for t, _ in named)}")
+    if finite:
+        for t, name in named:
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError(f"{name}: points must be finite")
+
+
+def _clouds(named, **checks):
+    """_check_clouds, then _points for each (tensor, name)."""
+    _check_clouds(named, **checks)
+    return [_points(t, name) for t, name in named]
+
+
+def _launches(n_clouds, per, name="max_clouds_per_launch"):
+    """(s0, s1) of the launches that send `n_clouds` clouds out at most `per` at a time. ValueError, at the call and not at
+    the first step, unless per is an integer >= 1."""
+    _at_least_one(per, name)
+    return ((s0, min(n_clouds, s0 + per)) for s0 in range(0, n_clouds, per))
+
+
+def _at_least_one(v, name):
+    if not isinstance(v, int) or isinstance(v, bool) or v < 1:
+        raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
+    return v
+
+
 def nn_dist(x, y, clamp, unit_norm=False):
     """d[b, i] = min_j ||x[b, i] - y[b, j]|| after clamping coordinates to [-clamp, clamp] (optionally unit-normalised)."""
     x, y = _points(x, "x"), _points(y, "y")
@@ -180,37 +233,16 @@ def assignment_kernel_shape(n_points):
     raise ValueError(f"the assignment kernel takes 1 .. {ASSIGN_MAX_POINTS} points per cloud, got {n_points}")
 
 
-def _positive_int(v, name):
-    if not isinstance(v, int) or isinstance(v, bool) or v < 1:
-        raise ValueError(f"{name} must be a positive integer, got {v!r}")
-    return v
-
-
 def _assignment_arguments(x, y, clamp, max_rounds, rounds_per_launch):
-    """ValueError for everything about the arguments that does not need the GPU (checked before the device, so it holds
-    for CPU tensors too). Returns (max_rounds, rounds_per_launch) with the defaults filled in."""
-    for t, name in ((x, "x"), (y, "y")):
-        if not torch.is_tensor(t):
-            raise ValueError(f"{name}: expected a tensor [B, n, 3], got {type(t).__name__}")
-        if t.dim() != 3 or t.shape[-1] != 3:
-            raise ValueError(f"{name}: expected [B, n, 3] points, got {tuple(t.shape)}")
-    if x.shape[0] != y.shape[0]:
-        raise ValueError(f"x holds {x.shape[0]} clouds, y {y.shape[0]}: the assignment pairs x[b] with y[b]")
-    if x.shape[1] != y.shape[1]:
-        raise ValueError(f"the assignment needs equal point counts (got {x.shape[1]} (x) and {y.shape[1]} (y))")
+    """_check_clouds and the operation's own arguments. Returns (max_rounds, rounds_per_launch) with the defaults filled in."""
+    _check_clouds(((x, "x"), (y, "y")), letters="B, n", count_range=("assignment", ASSIGN_MAX_POINTS), same_clouds=True,
+                  same_points="the assignment")
     n = x.shape[1]
-    if not 1 <= n <= ASSIGN_MAX_POINTS:
-        raise ValueError(f"the assignment kernel takes 1 .. {ASSIGN_MAX_POINTS} points per cloud, got {n}")
     if clamp is not None and not (isinstance(clamp, (int, float)) and not isinstance(clamp, bool) and 0 < clamp < math.inf):
         raise ValueError(f"clamp must be None or a positive finite number, got {clamp!r}")
-    max_rounds = 64 * n + 1024 if max_rounds is None else _positive_int(max_rounds, "max_rounds")
+    max_rounds = 64 * n + 1024 if max_rounds is None else _at_least_one(max_rounds, "max_rounds")
     rounds_per_launch = (max(16, _ASSIGN_COLUMN_VISITS_PER_LAUNCH // n) if rounds_per_launch is None
-                         else _positive_int(rounds_per_launch, "rounds_per_launch"))
-    if x.device != y.device:
-        raise ValueError(f"x is on {x.device}, y on {y.device}")
-    for t, name in ((x, "x"), (y, "y")):
-        if not bool(torch.isfinite(t).all()):
-            raise ValueError(f"{name}: points must be finite")
+                         else _at_least_one(rounds_per_launch, "rounds_per_launch"))
     return max_rounds, rounds_per_launch
 
 
@@ -273,17 +305,6 @@ EMD_MAX_POINTS = 4096  # == NOVA_EMD_MAX_POINTS of include/nova_hip.h
 _EMD_EVALUATIONS_PER_LAUNCH = 1 << 36  # (k, l, level) evaluations, ~6.9e10: tens of milliseconds per launch (profiles/emd_matrix_*)
 
 
-def _finite_points(*named):
-    """_points for each (tensor, name), after checking every tensor's shape and finiteness (ValueError) first."""
-    for t, name in named:
-        if torch.is_tensor(t):
-            if t.dim() != 3 or t.shape[-1] != 3:
-                raise ValueError(f"{name}: expected [S, n, 3] clouds, got {tuple(t.shape)}")
-            if not bool(torch.isfinite(t).all()):
-                raise ValueError(f"{name}: points must be finite")
-    return [_points(t, name) for t, name in named]
-
-
 def chamfer_matrix(x, y=None, max_pairs_per_launch=None):
     """cd[a, b] = CD(x[a], y[b]) for clouds x [A, N, 3] and y [B, M, 3] on the GPU: float32 [A, B] on x's device, with
 
@@ -294,9 +315,7 @@ def chamfer_matrix(x, y=None, max_pairs_per_launch=None):
     the result is exactly symmetric. The pair grid is split into launches of at most `max_pairs_per_launch` cloud pairs
     (default: ~1.4e11 squared distances each); every entry is bitwise the same whatever the split."""
     sym = y is None
-    x, y = _finite_points((x, "x")) * 2 if sym else _finite_points((x, "x"), (y, "y"))
-    if y.device != x.device:
-        raise ValueError(f"x is on {x.device}, y on {y.device}")
+    x, y = _clouds([(x, "x")]) * 2 if sym else _clouds([(x, "x"), (y, "y")])
     A, N, B, M = x.shape[0], x.shape[1], y.shape[0], y.shape[1]
     cd = torch.empty(A, B, dtype=torch.float32, device=x.device)
     if A == 0 or B == 0:
@@ -340,16 +359,6 @@ def _emd_resident_workgroups(device, N):
     return torch.cuda.get_device_properties(device).multi_processor_count * per_cu
 
 
-def _emd_point_counts(named):
-    """ValueError unless the [S, n, 3] tensors of `named` share one point count n in 1 .. EMD_MAX_POINTS (checked before
-    _finite_points, so it holds for CPU tensors too)."""
-    counts = {t.shape[1] for t, _ in named if torch.is_tensor(t) and t.dim() == 3}
-    if len(counts) > 1:
-        raise ValueError(f"the EMD needs equal point counts (got {' and '.join(f'{t.shape[1]} ({n})' for t, n in named)})")
-    if counts and not 1 <= min(counts) <= EMD_MAX_POINTS:
-        raise ValueError(f"the EMD kernel takes 1 .. {EMD_MAX_POINTS} points per cloud, got {min(counts)}")
-
-
 def emd_matrix(x, y=None, max_pairs_per_launch=None):
     """emd[a, b] = EMD(x[a], y[b]) for clouds x [A, N, 3] and y [B, N, 3] on the GPU: float32 [A, B] on x's device. The
     EMD is approxmatch followed by its match cost, divided by n (PointFlow's emd_approx; the algorithm is spelled out
@@ -360,10 +369,8 @@ def emd_matrix(x, y=None, max_pairs_per_launch=None):
     y=None is x against itself: the full matrix is computed (not mirrored). The pair grid is split into launches of at
     most `max_pairs_per_launch` cloud pairs (default: ~6.9e10 (k, l, level) evaluations each, in whole rounds of the
     resident workgroups); every entry is bitwise the same whatever the split."""
-    _emd_point_counts([(x, "x")] if y is None else [(x, "x"), (y, "y")])
-    x, y = _finite_points((x, "x")) * 2 if y is None else _finite_points((x, "x"), (y, "y"))
-    if y.device != x.device:
-        raise ValueError(f"x is on {x.device}, y on {y.device}")
+    emd_checks = dict(count_range=("EMD", EMD_MAX_POINTS), same_points="the EMD")
+    x, y = _clouds([(x, "x")], **emd_checks) * 2 if y is None else _clouds([(x, "x"), (y, "y")], **emd_checks)
     A, N, B = x.shape[0], x.shape[1], y.shape[0]
     emd = torch.empty(A, B, dtype=torch.float32, device=x.device)
     if A == 0 or B == 0:
@@ -441,9 +448,8 @@ def compute_all_metrics(sample_pcs, ref_pcs, batch_size=None, emd=False, jsd=Fal
     "jsd_outside_fraction", the larger of the two sets' shares of points outside the grid. Returns a dict of Python floats."""
     if jsd:
         _check_resolution(jsd_resolution, True)
-    if emd:
-        _emd_point_counts([(sample_pcs, "sample_pcs"), (ref_pcs, "ref_pcs")])
-    smp, ref = _finite_points((sample_pcs, "sample_pcs"), (ref_pcs, "ref_pcs"))
+    emd_checks = dict(count_range=("EMD", EMD_MAX_POINTS), same_points="the EMD") if emd else {}
+    smp, ref = _clouds([(sample_pcs, "sample_pcs"), (ref_pcs, "ref_pcs")], **emd_checks)
     if smp.shape[0] == 0 or ref.shape[0] == 0:
         raise ValueError("compute_all_metrics: empty set")
     d_rs = chamfer_matrix(ref, smp, batch_size)
@@ -507,7 +513,7 @@ def occupancy_grid(pclouds, resolution=28, in_sphere=True, return_nodes=False, m
     for every split: the set goes out in launches of at most `max_clouds_per_launch` clouds (default:
     _OCC_POINTS_PER_LAUNCH points each), and `workgroups` (0 = automatic) sets the kernel's grid size."""
     _check_resolution(resolution, in_sphere)
-    (x,) = _finite_points((pclouds, "pclouds"))
+    (x,) = _clouds([(pclouds, "pclouds")])
     S, N, R = x.shape[0], x.shape[1], resolution
     counters = torch.zeros(R ** 3, dtype=torch.int64, device=x.device)
     bernoulli = torch.zeros_like(counters)
@@ -517,12 +523,9 @@ def occupancy_grid(pclouds, resolution=28, in_sphere=True, return_nodes=False, m
         if N == 0:
             raise ValueError("occupancy_grid: empty clouds (0 points)")
         per = max_clouds_per_launch if max_clouds_per_launch is not None else max(1, _OCC_POINTS_PER_LAUNCH // N)
-        if per < 1:
-            raise ValueError(f"max_clouds_per_launch must be >= 1, got {per}")
         with torch.cuda.device(x.device):
             st = hip.stream_ptr()
-            for s0 in range(0, S, per):
-                s1 = min(S, s0 + per)
+            for s0, s1 in _launches(S, per):
                 hip.call("nova_pointset_occupancy_grid", x[s0].data_ptr(), counters.data_ptr(), bernoulli.data_ptr(),
                          nodes[s0].data_ptr() if return_nodes else None, outside.data_ptr(), s1 - s0, N, R, 1 if in_sphere else 0,
                          int(workgroups), st)
@@ -601,15 +604,9 @@ def fps_kernel_shape(n_points):
 
 
 def _fps_arguments(points, n_samples, start):
-    """ValueError for everything about the arguments that does not need the GPU (checked before the device, so it holds
-    for CPU tensors too). Returns `start` as None (index 0 everywhere) or an int64 CPU tensor [S]."""
-    if not torch.is_tensor(points):
-        raise ValueError(f"points: expected a tensor [S, N, 3], got {type(points).__name__}")
-    if points.dim() != 3 or points.shape[-1] != 3:
-        raise ValueError(f"points: expected [S, N, 3] clouds, got {tuple(points.shape)}")
+    """_check_clouds and the operation's own arguments. Returns `start` as None (index 0 everywhere) or an int64 CPU tensor [S]."""
+    _check_clouds([(points, "points")], letters="S, N", count_range=("FPS", FPS_MAX_POINTS))
     S, N = points.shape[0], points.shape[1]
-    if not 1 <= N <= FPS_MAX_POINTS:
-        raise ValueError(f"the FPS kernel takes 1 .. {FPS_MAX_POINTS} points per cloud, got {N}")
     if not isinstance(n_samples, int) or isinstance(n_samples, bool) or not 1 <= n_samples <= N:
         raise ValueError(f"n_samples must be an integer in 1 .. {N} (the point count), got {n_samples!r}")
     if isinstance(start, int) and not isinstance(start, bool):
@@ -623,8 +620,6 @@ def _fps_arguments(points, n_samples, start):
         st = st.long()
         if S > 0 and not (0 <= int(st.min()) and int(st.max()) < N):
             raise ValueError(f"start must be in 0 .. {N - 1}, got values in {int(st.min())} .. {int(st.max())}")
-    if not bool(torch.isfinite(points).all()):
-        raise ValueError("points: points must be finite")
     return st
 
 
@@ -642,17 +637,15 @@ def farthest_point_sample(points, n_samples, start=0, return_distances=False, ma
     x = _points(points, "points")
     S, N, n = x.shape[0], x.shape[1], n_samples
     per = max_clouds_per_launch if max_clouds_per_launch is not None else max(1, _FPS_POINT_STEPS_PER_LAUNCH // (N * n))
-    if per < 1:
-        raise ValueError(f"max_clouds_per_launch must be >= 1, got {per}")
+    launches = _launches(S, per)
     idx = torch.empty(S, n, dtype=torch.int32, device=x.device)
     dist = torch.empty(S, n, dtype=torch.float32, device=x.device) if return_distances else None
     st = st.to(device=x.device, dtype=torch.int32) if st is not None else None
-    if S > 0:
-        with torch.cuda.device(x.device):
-            stream = hip.stream_ptr()
-            for s0 in range(0, S, per):
-                hip.call("nova_pointset_farthest_point_sample", x[s0].data_ptr(), st[s0:].data_ptr() if st is not None else None,
-                         idx[s0].data_ptr(), dist[s0].data_ptr() if return_distances else None, min(S, s0 + per) - s0, N, n, stream)
+    with torch.cuda.device(x.device):
+        stream = hip.stream_ptr()
+        for s0, s1 in launches:
+            hip.call("nova_pointset_farthest_point_sample", x[s0].data_ptr(), st[s0:].data_ptr() if st is not None else None,
+                     idx[s0].data_ptr(), dist[s0].data_ptr() if return_distances else None, s1 - s0, N, n, stream)
     return (idx.long(), dist) if return_distances else idx.long()
 
 
@@ -666,11 +659,9 @@ def resample_clouds(points, n_points, method="fps", start=0, generator=None):
     than the clouds have is a ValueError."""
     if method not in RESAMPLE_METHODS:
         raise ValueError(f"method must be one of {RESAMPLE_METHODS}, got {method!r}")
-    if not torch.is_tensor(points) or points.dim() != 3 or points.shape[-1] != 3:
-        raise ValueError(f"points: expected [S, N, 3] clouds, got {tuple(points.shape) if torch.is_tensor(points) else type(points).__name__}")
+    _check_clouds([(points, "points")], letters="S, N", finite=False)
     S, N = points.shape[0], points.shape[1]
-    if not isinstance(n_points, int) or isinstance(n_points, bool) or n_points < 1:
-        raise ValueError(f"n_points must be a positive integer, got {n_points!r}")
+    _at_least_one(n_points, "n_points")
     if n_points > N:
         raise ValueError(f"cannot resample clouds of {N} points to {n_points}: resampling only removes points")
     if n_points == N:
@@ -710,20 +701,10 @@ def knn_kernel_shape(n_clouds, n_queries, k):
 
 
 def _knn_arguments(x, y, k, exclude_self):
-    """ValueError for everything about the arguments that does not need the GPU (checked before the device, so it holds
-    for CPU tensors too). Returns exclude_self resolved to a bool."""
-    for t, name in ((x, "x"),) + (((y, "y"),) if y is not None else ()):
-        if not torch.is_tensor(t):
-            raise ValueError(f"{name}: expected a tensor [S, N, 3], got {type(t).__name__}")
-        if t.dim() != 3 or t.shape[-1] != 3:
-            raise ValueError(f"{name}: expected [S, N, 3] clouds, got {tuple(t.shape)}")
-        if not 1 <= t.shape[1] <= KNN_MAX_POINTS:
-            raise ValueError(f"{name}: the kNN kernel takes 1 .. {KNN_MAX_POINTS} points per cloud, got {t.shape[1]}")
+    """_check_clouds and the operation's own arguments. Returns exclude_self resolved to a bool."""
+    _check_clouds([(x, "x")] + ([(y, "y")] if y is not None else []), letters="S, N", count_range=("kNN", KNN_MAX_POINTS),
+                  same_clouds=True)
     N, M = x.shape[1], (x if y is None else y).shape[1]
-    if y is not None and y.shape[0] != x.shape[0]:
-        raise ValueError(f"x and y must hold the same number of clouds, got {x.shape[0]} and {y.shape[0]}")
-    if y is not None and y.device != x.device:
-        raise ValueError(f"x and y must be on the same device, got {x.device} and {y.device}")
     if exclude_self is None:
         exclude_self = y is None
     if not isinstance(exclude_self, bool):
@@ -734,9 +715,6 @@ def _knn_arguments(x, y, k, exclude_self):
     if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= k_max:
         raise ValueError(f"k must be an integer in 1 .. {k_max} (at most {KNN_MAX_K}, and {M} target points"
                          f"{' without the point itself' if exclude_self else ''}), got {k!r}")
-    for t, name in ((x, "x"),) + (((y, "y"),) if y is not None else ()):
-        if not bool(torch.isfinite(t).all()):
-            raise ValueError(f"{name}: points must be finite")
     return exclude_self
 
 
@@ -760,16 +738,14 @@ def knn_points(x, y=None, k=8, exclude_self=None, return_distances=True, max_clo
     ys = xs if y is None else _points(y, "y")
     S, N, M = xs.shape[0], xs.shape[1], ys.shape[1]
     per = max_clouds_per_launch if max_clouds_per_launch is not None else max(1, _KNN_CANDIDATES_PER_LAUNCH // (N * M))
-    if not isinstance(per, int) or isinstance(per, bool) or per < 1:
-        raise ValueError(f"max_clouds_per_launch must be an integer >= 1, got {per!r}")
+    launches = _launches(S, per)
     idx = torch.empty(S, N, k, dtype=torch.int32, device=xs.device)
     d2 = torch.empty(S, N, k, dtype=torch.float32, device=xs.device) if return_distances else None
-    if S > 0:
-        with torch.cuda.device(xs.device):
-            stream = hip.stream_ptr()
-            for s0 in range(0, S, per):
-                hip.call("nova_pointset_knn", xs[s0].data_ptr(), ys[s0].data_ptr(), idx[s0].data_ptr(),
-                         d2[s0].data_ptr() if return_distances else None, min(S, s0 + per) - s0, N, M, k, 1 if exclude_self else 0, stream)
+    with torch.cuda.device(xs.device):
+        stream = hip.stream_ptr()
+        for s0, s1 in launches:
+            hip.call("nova_pointset_knn", xs[s0].data_ptr(), ys[s0].data_ptr(), idx[s0].data_ptr(),
+                     d2[s0].data_ptr() if return_distances else None, s1 - s0, N, M, k, 1 if exclude_self else 0, stream)
     return (idx.long(), d2) if return_distances else idx.long()
 
 

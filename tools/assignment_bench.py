@@ -25,6 +25,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from nova_pointcloud_amd import hip, metrics  # noqa: E402
+from pointset_bench_common import timed  # noqa: E402
 
 CASES = ((32, 512), (662, 512), (32, 2048), (662, 2048))
 CLAMP = 5.0
@@ -33,19 +34,6 @@ CLAMP = 5.0
 def clouds(B, n, seed):
     g = torch.Generator().manual_seed(seed)
     return torch.randn(B, n, 3, generator=g).clamp(-5, 5).cuda(), torch.randn(B, n, 3, generator=g).clamp(-5, 5).cuda()
-
-
-def timed(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    times = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        a.record()
-        out = fn()
-        b.record()
-        torch.cuda.synchronize()
-        times.append(a.elapsed_time(b) / 1e3)
-    return out, min(times), (max(times) - min(times)) / min(times)
 
 
 def host_path(x, y):

@@ -18,26 +18,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from nova_pointcloud_amd import metrics  # noqa: E402
+from pointset_bench_common import shell_clouds, timed_once  # noqa: E402
 
 VALU_BOUND = 8.0  # vector operations per distance
 LANES_PER_CLK = 32 * 1024
-
-
-def clouds(S, n, seed):
-    g = torch.Generator().manual_seed(seed)
-    p = torch.randn(S, n, 3, generator=g)
-    p = p / p.norm(dim=-1, keepdim=True) * (1 + 0.05 * torch.randn(S, n, 1, generator=g))
-    p = p * (0.5 + torch.rand(S, 1, 3, generator=g)) + 0.2 * torch.randn(S, 1, 3, generator=g)  # per-shape scale / offset
-    return p.cuda()
-
-
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    torch.cuda.synchronize()
-    return out, a.elapsed_time(b) / 1e3
 
 
 def torch_chamfer(x, y, chunk):
@@ -59,12 +43,12 @@ def main():
     ap.add_argument("--out")
     args = ap.parse_args()
     S, n = args.S, args.n
-    ref, smp = clouds(S, n, 1), clouds(S, n, 2)
+    ref, smp = shell_clouds(S, n, 1), shell_clouds(S, n, 2)
     metrics.chamfer_matrix(ref[:64], smp[:64])  # warm-up (library load, first launches)
     metrics.chamfer_matrix(ref[:64])
     torch.cuda.synchronize()
-    d_rs, t_rs = timed(lambda: metrics.chamfer_matrix(ref, smp))
-    (d_rr, d_ss), t_sym = timed(lambda: (metrics.chamfer_matrix(ref), metrics.chamfer_matrix(smp)))
+    d_rs, t_rs = timed_once(lambda: metrics.chamfer_matrix(ref, smp))
+    (d_rr, d_ss), t_sym = timed_once(lambda: (metrics.chamfer_matrix(ref), metrics.chamfer_matrix(smp)))
     pairs_rs, pairs_sym = S * S, S * (S + 1)  # two triangles with their diagonals
     dist_rs, dist_all = pairs_rs * n * n, (pairs_rs + pairs_sym) * n * n
     bound = LANES_PER_CLK * 2.4e9 / VALU_BOUND
@@ -77,7 +61,7 @@ def main():
     if not args.hip_only:
         torch_chamfer(ref[:1], smp[:args.chunk], args.chunk)  # warm-up
         torch.cuda.synchronize()
-        t_rs_torch = timed(lambda: torch_chamfer(ref, smp, args.chunk))
+        t_rs_torch = timed_once(lambda: torch_chamfer(ref, smp, args.chunk))
         d_torch, t_torch = t_rs_torch
         rel = ((d_torch - d_rs).abs() / d_rs).max().item()
         res.update({"torch_rs_s": round(t_torch, 4), "torch_rs_dist_per_s": dist_rs / t_torch,

@@ -20,27 +20,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from nova_pointcloud_amd import metrics  # noqa: E402
+from pointset_bench_common import shell_clouds, timed_once  # noqa: E402
 
 LEVELS = 10
 SIMD_CYCLES_PER_EVAL = 26 / 32 + 4 * 8 / 64
 SIMDS, CLOCK = 1024, 2.4e9
-
-
-def clouds(S, n, seed):
-    g = torch.Generator().manual_seed(seed)
-    p = torch.randn(S, n, 3, generator=g)
-    p = p / p.norm(dim=-1, keepdim=True) * (1 + 0.05 * torch.randn(S, n, 1, generator=g))
-    p = p * (0.5 + torch.rand(S, 1, 3, generator=g)) + 0.2 * torch.randn(S, 1, 3, generator=g)  # per-shape scale / offset
-    return p.cuda()
-
-
-def timed(fn):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    out = fn()
-    b.record()
-    torch.cuda.synchronize()
-    return out, a.elapsed_time(b) / 1e3
 
 
 def torch_emd(x, y):
@@ -81,11 +65,11 @@ def main():
     ap.add_argument("--out")
     args = ap.parse_args()
     S, n = args.S, args.n
-    ref, smp = clouds(S, n, 1), clouds(S, n, 2)
+    ref, smp = shell_clouds(S, n, 1), shell_clouds(S, n, 2)
     metrics.emd_matrix(ref[:32], smp[:32])  # warm-up (library load, first launches)
     torch.cuda.synchronize()
-    d_rs, t_rs = timed(lambda: metrics.emd_matrix(ref, smp))
-    (d_rr, d_ss), t_rr_ss = timed(lambda: (metrics.emd_matrix(ref), metrics.emd_matrix(smp)))
+    d_rs, t_rs = timed_once(lambda: metrics.emd_matrix(ref, smp))
+    (d_rr, d_ss), t_rr_ss = timed_once(lambda: (metrics.emd_matrix(ref), metrics.emd_matrix(smp)))
     evals_rs = S * S * n * n * LEVELS
     bound = SIMDS * CLOCK / SIMD_CYCLES_PER_EVAL
     t_all = t_rs + t_rr_ss
@@ -105,7 +89,7 @@ def main():
                                                    torch.randint(S, (args.torch_pairs,), generator=g))]
         torch_emd_pairs(ref, smp, pairs[:args.chunk], args.chunk)  # warm-up
         torch.cuda.synchronize()
-        d_torch, t_torch = timed(lambda: torch_emd_pairs(ref, smp, pairs, args.chunk))
+        d_torch, t_torch = timed_once(lambda: torch_emd_pairs(ref, smp, pairs, args.chunk))
         hip_sub = torch.stack([d_rs[a, b] for a, b in pairs])
         rel = ((d_torch - hip_sub).abs() / hip_sub).max().item()
         per_pair_torch, per_pair_hip = t_torch / len(pairs), t_rs / (S * S)

@@ -25,16 +25,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from nova_pointcloud_amd import metrics  # noqa: E402
+from pointset_bench_common import ball_clouds, timed  # noqa: E402
 
 SHAPES = ((15000, 2048), (2048, 512))
 REL = 1e-6
-
-
-def clouds(S, N, seed):
-    """Points in the ball of radius 0.5, denser towards the centre (a shape-like, non-uniform cloud)."""
-    g = torch.Generator().manual_seed(seed)
-    p = torch.randn(S, N, 3, generator=g)
-    return (p / p.norm(dim=-1, keepdim=True) * 0.5 * torch.rand(S, N, 1, generator=g)).cuda()
 
 
 def torch_fps(x, n):
@@ -48,19 +42,6 @@ def torch_fps(x, n):
         cur = mind.argmax(dim=1)
         idx[:, i] = cur
     return idx
-
-
-def timed(fn, reps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    times = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        a.record()
-        out = fn()
-        b.record()
-        torch.cuda.synchronize()
-        times.append(a.elapsed_time(b) / 1e3)
-    return out, min(times), (max(times) - min(times)) / min(times)
 
 
 def worst_shortfall(x, idx, chunk=64):
@@ -97,7 +78,7 @@ def main():
     S = args.S
     res = {"S": S, "reps": args.reps, "launch_cap_point_steps": metrics._FPS_POINT_STEPS_PER_LAUNCH, "shapes": {}}
     for N, n in SHAPES:
-        x = clouds(S, N, N)
+        x = ball_clouds(S, N, N)
         metrics.farthest_point_sample(x[:8], n)  # warm-up (library load, first launch)
         # one launch for the whole set, whatever the cap: the kernel time of the case
         (idx, dist), t, spread = timed(lambda: metrics.farthest_point_sample(x, n, return_distances=True, max_clouds_per_launch=S), args.reps)

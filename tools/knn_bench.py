@@ -24,18 +24,11 @@ import os
 import subprocess
 import sys
 
+from pointset_bench_common import ball_clouds, timed
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = {"32x2048k8": (32, 2048, 8), "1x15000k8": (1, 15000, 8), "662x2048k8": (662, 2048, 8), "662x2048k32": (662, 2048, 32)}
 REL = 1e-6
-
-
-def clouds(S, N, seed):
-    """Points in the ball of radius 0.5, denser towards the centre (a shape-like, non-uniform cloud)."""
-    import torch
-
-    g = torch.Generator().manual_seed(seed)
-    p = torch.randn(S, N, 3, generator=g)
-    return (p / p.norm(dim=-1, keepdim=True) * 0.5 * torch.rand(S, N, 1, generator=g)).cuda()
 
 
 def torch_knn(x, k, chunk):
@@ -48,21 +41,6 @@ def torch_knn(x, k, chunk):
         idx.append(i[..., 1:])
         d.append(v[..., 1:])
     return torch.cat(idx), torch.cat(d)
-
-
-def timed(fn, reps):
-    import torch
-
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    times = []
-    for _ in range(reps):
-        torch.cuda.synchronize()
-        a.record()
-        out = fn()
-        b.record()
-        torch.cuda.synchronize()
-        times.append(a.elapsed_time(b) / 1e3)
-    return out, min(times), (max(times) - min(times)) / min(times)
 
 
 def worst_excess(x, idx, d2, k, n_clouds=4):
@@ -86,7 +64,7 @@ def run_case(name, reps, hip_only):
     from nova_pointcloud_amd import metrics
 
     S, N, k = CASES[name]
-    x = clouds(S, N, N + k)
+    x = ball_clouds(S, N, N + k)
     metrics.knn_points(x[:2], k=k)  # warm-up (library load, first launch)
     (idx, d2), t, spread = timed(lambda: metrics.knn_points(x, k=k, max_clouds_per_launch=S), reps)
     _, t_api, _ = timed(lambda: metrics.knn_points(x, k=k), reps)

@@ -1,0 +1,50 @@
+"""Seeded inputs and device-event timers shared by the point-set bench tools (chamfer_matrix_bench, emd_matrix_bench,
+fps_bench, assignment_bench, knn_bench). torch is imported on first use: knn_bench's parent process does no GPU work."""
+
+
+def ball_clouds(S, N, seed):
+    """Points in the ball of radius 0.5, denser towards the centre (a shape-like, non-uniform cloud)."""
+    import torch
+
+    g = torch.Generator().manual_seed(seed)
+    p = torch.randn(S, N, 3, generator=g)
+    return (p / p.norm(dim=-1, keepdim=True) * 0.5 * torch.rand(S, N, 1, generator=g)).cuda()
+
+
+def shell_clouds(S, n, seed):
+    """Noisy unit spheres, each cloud with a scale and an offset of its own."""
+    import torch
+
+    g = torch.Generator().manual_seed(seed)
+    p = torch.randn(S, n, 3, generator=g)
+    p = p / p.norm(dim=-1, keepdim=True) * (1 + 0.05 * torch.randn(S, n, 1, generator=g))
+    p = p * (0.5 + torch.rand(S, 1, 3, generator=g)) + 0.2 * torch.randn(S, 1, 3, generator=g)  # per-shape scale / offset
+    return p.cuda()
+
+
+def timed_once(fn):
+    """(result, seconds) of one call between two device events."""
+    import torch
+
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    out = fn()
+    b.record()
+    torch.cuda.synchronize()
+    return out, a.elapsed_time(b) / 1e3
+
+
+def timed(fn, reps):
+    """(result, best seconds, (max - min) / min) over `reps` calls, each between two device events."""
+    import torch
+
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        a.record()
+        out = fn()
+        b.record()
+        torch.cuda.synchronize()
+        times.append(a.elapsed_time(b) / 1e3)
+    return out, min(times), (max(times) - min(times)) / min(times)
