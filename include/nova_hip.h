@@ -372,6 +372,51 @@ int nova_pointset_farthest_point_sample(const float* x, const int* start, int* i
 #define NOVA_KNN_MAX_POINTS 65536
 int nova_pointset_knn(const float* x, const float* y, int* idx, float* d2, int S, int N, int M, int k, int exclude_self, void* stream);
 
+/* Distance-weighted interpolation: for every query point of q [S, T, 3] the average of the values v [S, N, C] of ALL source
+ * points p [S, N, 3] of its cloud (float32, finite), weighted by softmax(-distance / temperature), without ever storing a
+ * [T, N] matrix. It is the reference's feature_aware_interpolation,
+ * diffnext/models/transformers/transformer_pointcloud_nova.py:128-152 (torch.cdist(target, points), softmax(-dist), then
+ * sum(weights.unsqueeze(-1) * points.unsqueeze(1)): an [S, T, N, 3] float tensor, summed away at once), the dense branch
+ * of adaptive_sampling at :92-97, with the values made an argument and the temperature (1 there) a parameter.
+ * NOT REPRODUCED: that body also takes topk(k = 8) of the distance matrix (:144-146) and never uses the result: dead code.
+ * DEVIATION of the Python caller, on purpose: adaptive_sampling at :92-97 sends a subset with fewer points than target_size
+ * to farthest_point_sampling with more samples than points, which that body cannot deliver; metrics.adaptive_sampling
+ * returns the points in farthest-point order, repeated cyclically (every prefix stays well spread).
+ * v == NULL means "the values are the source points" and needs C == 3. q may be the same pointer as p; out must not
+ * overlap an input. For query i of cloud s, with sqdist3 the expression of nova_pointset_knn (three exact-difference
+ * subtractions, one rounded product, two fused multiply-adds):
+ *   d_j    = sqrtf(sqdist3(q[s, i], p[s, j]))            correctly rounded square root
+ *   m      = min_j d_j
+ *   w_j    = exp2f((m - d_j) * scale)                     scale = log2(e) / temperature in float32, made by the caller;
+ *                                                        the difference and the product rounded once each, exp2f the
+ *                                                        hardware's v_exp_f32 (1 ulp; results below 2^-126 become 0)
+ *   out[s, i, c] = (sum_j w_j * v[s, j, c]) / (sum_j w_j)  one IEEE-rounded division, no reciprocal approximation
+ * The point itself is not excluded (the reference's targets are a subset of its sources). scale == 0 (temperature = +inf)
+ * is legal and gives the plain mean. The minimum is subtracted before exp2f, so queries far from every source are served
+ * like near ones.
+ * Order of summation (part of the definition: it fixes the bits). Always one workgroup of 256 threads per 64 queries, one
+ * query per lane in all four waves; wave w sums the 64-source chunks w, w + 4, w + 8, ... of the cloud in ascending index
+ * order, in the online form: its minimum m starts at the distance of its first source and its sums l, a[c] at 0; per
+ * source, if d < m then l and a[c] are multiplied by exp2f((d - m) * scale) and m = d; then w = exp2f((m - d) * scale),
+ * l = l + w, a[c] = fmaf(w, v[c], a[c]). The four partials are merged in wave order: M = the minimum of the m of the waves
+ * that saw a source (wave w does when N > 64 w; the others contribute nothing), f_w = exp2f((M - m_w) * scale),
+ * L = l_0 * f_0, A[c] = a_0[c] * f_0, then for w = 1 .. 3 L = fmaf(l_w, f_w, L), A[c] = fmaf(a_w[c], f_w, A[c]);
+ * out = A[c] / L. No infinity enters this arithmetic, so scale == 0 meets neither inf * 0 nor inf - inf.
+ * Consequences:
+ *   - the result depends on (q[s], p[s], v[s], C, scale) alone: bitwise the same for every batch size, launch split and
+ *     position in the batch, and a channel's result does not depend on the other channels;
+ *   - v == NULL is bitwise equal to passing a copy of p as v with C = 3;
+ *   - where every w_j is exactly 0 or 1 and the sums are exact in float32 (integer values, scale == 0 or a temperature far
+ *     below the spacing of the distances) the result is the correctly rounded quotient of the exact sums.
+ * Squared distances must be finite in float32 (coordinates below about 1e19 in magnitude).
+ * NOVA_ERR_SHAPE for T or N outside 1 .. NOVA_INTERP_MAX_POINTS and for C outside 1 .. NOVA_INTERP_MAX_CHANNELS (the
+ * numerators of a query live in registers); NOVA_ERR_ARG for v == NULL with C != 3, for scale negative, NaN or infinite,
+ * and for null q, p or out with S > 0. S <= 0 returns 0 after those checks. Everything is checked before any device work. */
+#define NOVA_INTERP_MAX_POINTS 65536
+#define NOVA_INTERP_MAX_CHANNELS 8
+int nova_pointset_kernel_interpolate(const float* q, const float* p, const float* v, float* out,
+                                     int S, int T, int N, int C, float scale, void* stream);
+
 /* Optimal assignment between x [B, n, 3] and y [B, n, 3] (float32, finite), pair by pair: the permutation that minimises
  * the mean matched distance, i.e. the earth mover's distance that compute_emd_distance (test_optimize.py:385-415) and
  * emd_approx (train_newloss.py:352-372) take from scipy's linear_sum_assignment on a [n, n] cost matrix copied to the

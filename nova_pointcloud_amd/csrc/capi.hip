@@ -488,6 +488,11 @@ int nova_pointset_knn(const float* x, const float* y, int* idx, float* d2, int S
   return pointset_knn(x, y, idx, d2, S, N, M, k, exclude_self, (hipStream_t)stream);
 }
 
+int nova_pointset_kernel_interpolate(const float* q, const float* p, const float* v, float* out, int S, int T, int N, int C, float scale,
+                                     void* stream) {
+  return pointset_kernel_interpolate(q, p, v, out, S, T, N, C, scale, (hipStream_t)stream);
+}
+
 long long nova_pointset_assignment_state_bytes(int n) { return (long long)pointset_assignment_state_bytes(n); }
 
 int nova_pointset_assignment(const float* x, const float* y, int* col_of_row, float* cost, void* state, int B, int n, float clamp_lo,

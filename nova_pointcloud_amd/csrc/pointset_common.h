@@ -1,4 +1,4 @@
-// Device helpers shared by the point-set kernels (pointset, chamfer, emd, occupancy, fps, assign, knn): every result of
+// Device helpers shared by the point-set kernels (pointset, chamfer, emd, occupancy, fps, assign, knn, interp): every result of
 // that family is bitwise the same for every batch and launch split, which rests on all of them computing one distance
 // expression and summing in one fixed order. Both are defined here once.
 #pragma once

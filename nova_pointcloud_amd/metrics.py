@@ -32,6 +32,10 @@ and robust_emd.
 Local statistics of a cloud: knn_points (csrc/knn.hip), the exact k nearest neighbours of every point with their squared
 distances and no [N, M] matrix, and local_density on it, the reference's compute_local_density
 (transformer_pointcloud_nova.py:81-89) with the point itself excluded by index rather than by dropping a column.
+
+Thinning a dense cloud without dropping points: kernel_interpolate (csrc/interp.hip), every query the softmax(-distance /
+temperature) average of all source values with no [T, N] matrix, and on it the reference's feature_aware_interpolation
+(transformer_pointcloud_nova.py:128-152) and adaptive_sampling (:92-97).
 """
 import json
 import math
@@ -756,6 +760,139 @@ def local_density(points, k_neighbors=8):
     by index (knn_points), so the distances are the same multiset and a duplicate of the point counts at distance 0."""
     _, d2 = knn_points(points, k=k_neighbors)
     return d2.sqrt().mean(dim=-1)
+
+
+# ----------------------------------------------------------------------------------------------------
+# distance-weighted interpolation and adaptive sampling
+# ----------------------------------------------------------------------------------------------------
+INTERP_MAX_POINTS = 65536  # == NOVA_INTERP_MAX_POINTS of include/nova_hip.h
+INTERP_MAX_CHANNELS = 8  # == NOVA_INTERP_MAX_CHANNELS of include/nova_hip.h
+# (query, source) pairs (clouds x queries x sources) per launch, ~8.6e9. Re-derived from the measured launches of
+# tools/interp_bench.py (profiles/interp_bench.json): 32 x 1024 queries on 2048 sources, 512 workgroups, run in 0.21 ms
+# (3.1e11 pairs/s) and 7500 queries on 15 000 sources, 118 workgroups on 256 compute units, in 0.58 ms, the longest single
+# launch under this cap (1.9e11 pairs/s). Both are too small to fill the chip, so they are far below the instruction-count
+# estimate (about 46 vector issue slots per pair: ~1.7e12 pairs/s), and a full launch has not been timed; at the better of
+# the two measured rates 2^33 pairs are 28 ms, at the estimate 5 ms. A cloud is at most 2^32 pairs, so a launch holds at
+# least two (DESIGN.md, distance-weighted interpolation).
+_INTERP_PAIRS_PER_LAUNCH = 1 << 33
+
+
+def _interp_scale(temperature):
+    """log2(e) / temperature as the float32 the kernel takes. ValueError unless temperature is a real number > 0 (inf
+    allowed: the plain mean) and that quotient is finite in float32."""
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not temperature > 0:
+        raise ValueError(f"temperature must be a real number > 0 (inf for the plain mean), got {temperature!r}")
+    with np.errstate(over="ignore"):
+        scale = float(np.float32(np.float64(math.log2(math.e)) / np.float64(temperature)))  # one division in float64, one rounding
+    if not math.isfinite(scale):
+        raise ValueError(f"temperature {temperature!r} is too small: log2(e) / temperature is not finite in float32")
+    return scale
+
+
+def _interp_arguments(queries, points, values):
+    """_check_clouds and the checks of `values` that do not need the GPU. Returns the channel count C."""
+    _check_clouds([(queries, "queries"), (points, "points")], letters="S, N", count_range=("interpolation", INTERP_MAX_POINTS),
+                  same_clouds=True)
+    if values is None:
+        return 3
+    if not torch.is_tensor(values):
+        raise ValueError(f"values: expected a tensor [S, N, C], got {type(values).__name__}")
+    S, N = points.shape[0], points.shape[1]
+    if values.dim() != 3 or tuple(values.shape[:2]) != (S, N):
+        raise ValueError(f"values: expected [{S}, {N}, C] (one row per source point), got {tuple(values.shape)}")
+    if not 1 <= values.shape[2] <= INTERP_MAX_CHANNELS:
+        raise ValueError(f"values: the interpolation kernel takes 1 .. {INTERP_MAX_CHANNELS} channels, got {values.shape[2]}")
+    if not values.dtype.is_floating_point:
+        raise ValueError(f"values: expected a floating-point tensor, got {values.dtype}")
+    if values.device != points.device:
+        raise ValueError(f"values and points must be on the same device, got {values.device} and {points.device}")
+    if not bool(torch.isfinite(values).all()):
+        raise ValueError("values: values must be finite")
+    return values.shape[2]
+
+
+def kernel_interpolate(queries, points, values=None, temperature=1.0, max_clouds_per_launch=None):
+    """Distance-weighted interpolation on the GPU: float32 [S, T, C] on the input's device, row (s, i) the average of
+    values[s] [N, C] over ALL source points points[s] [N, 3], weighted by softmax_j(-|queries[s, i] - points[s, j]| /
+    temperature) (1 <= T, N <= 65536, 1 <= C <= 8). values=None means the source points themselves (C = 3), which is the
+    sum of the reference's feature_aware_interpolation (transformer_pointcloud_nova.py:149-150) without its [T, N] matrix
+    and its [S, T, N, 3] product. The point itself is not excluded; the nearest distance is subtracted before the
+    exponential, so far queries are served like near ones. temperature=inf is the plain mean. The definition and its
+    order of summation are spelled out in include/nova_hip.h at nova_pointset_kernel_interpolate (csrc/interp.hip).
+
+    ValueError for a temperature that is not a real number > 0 or so small that log2(e) / temperature is not finite in
+    float32, and for values that are not floating point, not finite or not [S, N, 1 .. 8] on the points' device.
+
+    The set goes out in launches of at most `max_clouds_per_launch` clouds (default: _INTERP_PAIRS_PER_LAUNCH (query,
+    source) pairs each); a cloud's result depends on (queries[s], points[s], values[s], temperature) alone and is bitwise
+    the same for every split. values=None is bitwise what values=points.clone() gives."""
+    C = _interp_arguments(queries, points, values)
+    scale = _interp_scale(temperature)
+    qs = _points(queries, "queries")
+    ps = qs if points is queries else _points(points, "points")
+    vs = None
+    if values is not None:
+        if not values.is_cuda:
+            raise hip.NovaHipError("values: point-set metrics run on the GPU (got a CPU tensor)")
+        if values.requires_grad and torch.is_grad_enabled():
+            raise hip.NovaHipError("values: nova_pointcloud_amd.metrics is evaluation-only (no autograd through the HIP kernels); detach the values")
+        vs = values.detach().float().contiguous()
+    S, T, N = qs.shape[0], qs.shape[1], ps.shape[1]
+    per = max_clouds_per_launch if max_clouds_per_launch is not None else max(1, _INTERP_PAIRS_PER_LAUNCH // (T * N))
+    launches = _launches(S, per)
+    out = torch.empty(S, T, C, dtype=torch.float32, device=qs.device)
+    with torch.cuda.device(qs.device):
+        stream = hip.stream_ptr()
+        for s0, s1 in launches:
+            hip.call("nova_pointset_kernel_interpolate", qs[s0].data_ptr(), ps[s0].data_ptr(), vs[s0].data_ptr() if vs is not None else None,
+                     out[s0].data_ptr(), s1 - s0, T, N, C, scale, stream)
+    return out
+
+
+def _cyclic(points, target_size):
+    """points [S, N, 3] repeated along the point axis and cut to target_size (pure torch)."""
+    return points.repeat(1, target_size // points.shape[1] + 1, 1)[:, :target_size]
+
+
+def _sampling_arguments(points, name, target_size, temperature):
+    _check_clouds([(points, name)], letters="S, N", finite=False)
+    _at_least_one(target_size, "target_size")
+    if points.shape[1] < 1:
+        raise ValueError(f"{name}: empty clouds (0 points)")
+    _interp_scale(temperature)
+
+
+def feature_aware_interpolation(points, target_size, temperature=1.0, generator=None):
+    """The reference's feature_aware_interpolation (transformer_pointcloud_nova.py:128-152): points [S, N, 3] thinned to
+    [S, target_size, 3] without dropping a point's contribution. With N <= target_size the points are repeated cyclically
+    and cut to target_size (pure torch; works on CPU tensors). Otherwise target_size of the points are picked by one
+    torch.randperm(N, generator=generator) shared by all clouds (a CPU generator, or None for the global one), as in the
+    reference, and each becomes kernel_interpolate's softmax(-distance / temperature) average of ALL N points (GPU only;
+    float32). The reference's temperature is 1; its topk(8) is dead code and is not reproduced."""
+    _sampling_arguments(points, "points", target_size, temperature)
+    N = points.shape[1]
+    if N <= target_size:
+        return _cyclic(points, target_size)
+    perm = torch.randperm(N, generator=generator)[:target_size].to(points.device)
+    return kernel_interpolate(points[:, perm], points, temperature=temperature)
+
+
+def adaptive_sampling(subset, target_size, temperature=1.0, generator=None):
+    """The reference's adaptive_sampling (transformer_pointcloud_nova.py:92-97): subset [S, N, 3] brought to
+    [S, target_size, 3]. N == target_size returns the input itself; N > target_size (a dense subset) returns
+    feature_aware_interpolation(subset, target_size, temperature, generator); N < target_size (a sparse one) returns the
+    points in farthest-point order (farthest_point_sample(subset, N)), repeated cyclically to target_size, so every prefix
+    of the result stays well spread (GPU only).
+    DEVIATION, on purpose: the reference sends the sparse case to its farthest_point_sampling with more samples than
+    points, which that body cannot deliver (include/nova_hip.h, nova_pointset_kernel_interpolate)."""
+    _sampling_arguments(subset, "subset", target_size, temperature)
+    S, N = subset.shape[0], subset.shape[1]
+    if N == target_size:
+        return subset
+    if N > target_size:
+        return feature_aware_interpolation(subset, target_size, temperature=temperature, generator=generator)
+    order = farthest_point_sample(subset, N)[:, torch.arange(target_size, device=subset.device) % N]
+    return torch.gather(subset, 1, order[:, :, None].expand(S, target_size, 3))
 
 
 NORMALIZE_MODES = ("none", "unit_sphere", "unit_cube")

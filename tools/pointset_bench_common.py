@@ -1,5 +1,6 @@
 """Seeded inputs and device-event timers shared by the point-set bench tools (chamfer_matrix_bench, emd_matrix_bench,
-fps_bench, assignment_bench, knn_bench). torch is imported on first use: knn_bench's parent process does no GPU work."""
+fps_bench, assignment_bench, knn_bench, interp_bench). torch is imported on first use: knn_bench's and interp_bench's parent
+processes do no GPU work."""
 
 
 def ball_clouds(S, N, seed):
