@@ -6,7 +6,11 @@
 //   d_gate = dy u2;  du2 = dy gate;  d_scale = du2 u1;  d_shift = du2;  du1 = du2 (1 + scale)
 //   d_gamma += du1 n;  d_beta += du1;  dn = du1 gamma;  dx = rstd (dn - mean(dn) - n mean(dn n));  d_res = dy (the caller's)
 // One wave per row, the whole row in registers, 16-byte accesses, statistics recomputed from x (nothing but x is kept by the
-// forward); a wave walks rows w, w + W, ... and keeps its lanes' d_gamma / d_beta sums in registers, written once per wave
+// forward) in f64: n = (x - mean) rstd is the correctly rounded f32 of the exact value also where x - mean cancels, so that
+// d_gamma's only errors are its own f32 products and sums (rows * 2^-23 * sum |term|; an f32 mean alone is off by 2^-24 |mean|,
+// many ulps of a small x - mean). About nine f64 issues per element; measured 1-4 % over the f32 statistics on bf16 rows of 768 to
+// 1536, 11 % on f32 rows of 1536 (8 chunks per lane, one wave per SIMD). dx stays f32 arithmetic on that n.
+// A wave walks rows w, w + W, ... and keeps its lanes' d_gamma / d_beta sums in registers, written once per wave
 // as a partial row ([waves, D] f32, summed by the caller): no atomics, bitwise reproducible. HBM-bound like the forward:
 // reads x, dy (+ the modulation rows it needs), writes dx (+ d_scale / d_shift / d_gate).
 #include "common.h"
@@ -32,6 +36,37 @@ struct RowNormBwdArgs {
   float eps;
 };
 
+// wave_sum of common.h on an f64: the same lane pairing, each step moving the two halves of the value
+template <int CTRL> __device__ __forceinline__ double dpp_move(double v) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  const uint32_t lo = dpp_move<CTRL>((uint32_t)u), hi = dpp_move<CTRL>((uint32_t)(u >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+__device__ __forceinline__ double pack_f64(uint32_t lo, uint32_t hi) { return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo)); }
+__device__ __forceinline__ double wave_sum(double v) {
+  v += dpp_move<0x141>(v);
+  v += dpp_move<0xb1>(v);
+  v += dpp_move<0x4e>(v);
+  v += dpp_move<0x140>(v);
+  {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    const auto lo = __builtin_amdgcn_permlane16_swap((uint32_t)u, (uint32_t)u, false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap((uint32_t)(u >> 32), (uint32_t)(u >> 32), false, false);
+    v = pack_f64(lo[0], hi[0]) + pack_f64(lo[1], hi[1]);
+  }
+  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+  const auto lo = __builtin_amdgcn_permlane32_swap((uint32_t)u, (uint32_t)u, false, false);
+  const auto hi = __builtin_amdgcn_permlane32_swap((uint32_t)(u >> 32), (uint32_t)(u >> 32), false, false);
+  return pack_f64(lo[0], hi[0]) + pack_f64(lo[1], hi[1]);
+}
+// 1 / sqrt(v) to f64 accuracy: the hardware estimate (v_rsq_f64, about 2^-26) and two Newton steps r (1.5 - 0.5 v r^2), each
+// squaring the relative error; once per row
+__device__ __forceinline__ double rsqrt_f64(double v) {
+  double r = __builtin_amdgcn_rsq(v);
+  r = r * fma(-0.5 * v * r, r, 1.5);
+  return r * fma(-0.5 * v * r, r, 1.5);
+}
+
 template <typename T, int NIT, bool HAS_MOD>
 __global__ __launch_bounds__(256) void row_norm_bwd_kernel(RowNormBwdArgs a) {
   using C = Chunk<T>;
@@ -51,7 +86,7 @@ __global__ __launch_bounds__(256) void row_norm_bwd_kernel(RowNormBwdArgs a) {
       dgam[it][k] = f4v{0.f, 0.f, 0.f, 0.f};
       dbet[it][k] = f4v{0.f, 0.f, 0.f, 0.f};
     }
-  const float inv_d = 1.0f / (float)a.D;
+  const double inv_d = 1.0 / (double)a.D;
   for (long row = wave; row < a.rows; row += nwaves) {
     const T* xp = static_cast<const T*>(a.x) + row * a.D;
     const T* dyp = static_cast<const T*>(a.dy) + row * a.D;
@@ -68,14 +103,16 @@ __global__ __launch_bounds__(256) void row_norm_bwd_kernel(RowNormBwdArgs a) {
         if (has_gate && has_ss) mb[it] = C::load(mp + a.shift_off + d);
       }
     }
-    float sum = 0.f;
+    double sum = 0.0;
 #pragma unroll
     for (int it = 0; it < NIT; ++it)
       if ((it * 64 + lane) * C::N < a.D)
 #pragma unroll
-        for (int k = 0; k < NV; ++k) sum += (x[it].v[k][0] + x[it].v[k][1]) + (x[it].v[k][2] + x[it].v[k][3]);
-    const float mean = wave_sum(sum) * inv_d;
-    float sq = 0.f;
+        for (int k = 0; k < NV; ++k)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) sum += (double)x[it].v[k][j];
+    const double mean = wave_sum(sum) * inv_d;
+    double sq = 0.0;
 #pragma unroll
     for (int it = 0; it < NIT; ++it)
       if ((it * 64 + lane) * C::N < a.D)
@@ -83,10 +120,11 @@ __global__ __launch_bounds__(256) void row_norm_bwd_kernel(RowNormBwdArgs a) {
         for (int k = 0; k < NV; ++k)
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const float c = x[it].v[k][j] - mean;
-            sq += c * c;
+            const double c = (double)x[it].v[k][j] - mean;
+            sq = fma(c, c, sq);
           }
-    const float rstd = rsqrtf(wave_sum(sq) * inv_d + a.eps);
+    const double rstd64 = rsqrt_f64(wave_sum(sq) * inv_d + (double)a.eps);
+    const float rstd = (float)rstd64;
     // n ends up in x, dn in dy; the modulation gradients are stored as soon as they are formed
     T* dmp = (HAS_MOD && a.dmod) ? static_cast<T*>(a.dmod) + row * a.mod_ld : nullptr;
     float s1 = 0.f, s2 = 0.f;
@@ -97,7 +135,9 @@ __global__ __launch_bounds__(256) void row_norm_bwd_kernel(RowNormBwdArgs a) {
         C dsc, dsh, dgt;
 #pragma unroll
         for (int k = 0; k < NV; ++k) {
-          const f4v n = (x[it].v[k] - mean) * rstd;
+          f4v n;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) n[j] = (float)(((double)x[it].v[k][j] - mean) * rstd64);
           const f4v u1 = n * gam[it][k] + bet[it][k];
           f4v g = dy[it].v[k];
           if (has_gate) {
@@ -124,7 +164,7 @@ __global__ __launch_bounds__(256) void row_norm_bwd_kernel(RowNormBwdArgs a) {
         }
       }
     }
-    const float m1 = wave_sum(s1) * inv_d, m2 = wave_sum(s2) * inv_d;
+    const float m1 = wave_sum(s1) * (float)inv_d, m2 = wave_sum(s2) * (float)inv_d;
     T* dxp = static_cast<T*>(a.dx) + row * a.D;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
