@@ -196,6 +196,13 @@ __device__ __forceinline__ f4v rope_rotate4(f4v x, f4v t) {
 
 // XCD-aware, bijective remap of a 1-D block id: blocks that share an XCD (id % 8) get a
 // contiguous chunk of the logical tile list, so neighbouring tiles hit the same per-XCD L2.
+// xcd_chunk: first tile and size of XCD `xcd`'s chunk of a list of nwg tiles, for a kernel that walks its chunk itself (the two
+// remaps below spell the same split out: through xcd_chunk the row-norm kernel's registers are allocated differently).
+__device__ __forceinline__ void xcd_chunk(int xcd, int nwg, int& base, int& size) {
+  const int q = nwg >> 3, r = nwg & 7;
+  base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
+  size = q + (xcd < r ? 1 : 0);
+}
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, k = bid >> 3;
   const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
@@ -210,6 +217,16 @@ __device__ __forceinline__ int xcd_remap_dir(int bid, int nwg, bool rev) {
   const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
   const int size = q + (xcd < r ? 1 : 0);
   return base + (rev ? size - 1 - k : k);
+}
+
+// Grouped order of the GEMM tile list (every GEMM structure): groups of gm row panels x all ntn column panels, row panel
+// fastest inside a group (the last group may be shorter), so the tiles in flight share few rows of A and W (L2 reuse).
+__device__ __forceinline__ void grouped_tile(int t, int ntm, int ntn, int gm, int& tm, int& tn) {
+  const int per_group = gm * ntn;
+  const int group = t / per_group, first_m = group * gm;
+  const int gsz = min(ntm - first_m, gm);
+  tm = first_m + (t % per_group) % gsz;
+  tn = (t % per_group) / gsz;
 }
 
 }  // namespace nova

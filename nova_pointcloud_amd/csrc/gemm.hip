@@ -22,19 +22,6 @@ namespace nova {
 
 constexpr int ROWB = 128;       // bytes of K per tile row
 
-struct GemmEpi {
-  const float* bias;     // [N] or nullptr
-  const float* rope;     // [rope_batch, L, hd/2, 2] (cos, sin) or nullptr
-  int L;                 // tokens per sequence (rows m -> (s = m / L, l = m % L))
-  int rope_batch;        // table batch count; sequence s uses table s % rope_batch
-  int hd;                // head dim
-  int rope_cols;         // columns [0, rope_cols) are rotated (q and k thirds of the fused QKV)
-  float q_scale;         // columns [0, q_cols) are multiplied by this after rotation (softmax scale folded into q)
-  int q_cols;
-};
-
-enum { EPI_NONE = 0, EPI_GELU = 1, EPI_SILU = 2, EPI_ROPE = 3 };
-
 template <typename T> struct Frag;   // one 16-byte LDS read = the per-lane K slice of a fragment
 template <> struct Frag<bf16_t> { u4v v; };
 template <> struct Frag<f16_t> { u4v v; };
@@ -77,14 +64,8 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const T* __restrict__ A, c
   const int wm = wid >> 1, wn = wid & 1;
 
   // XCD-aware + grouped tile order: 8 row panels x all column panels per group, row fastest.
-  const int nwg = ntm * ntn;
-  const int t = xcd_remap(blockIdx.x, nwg);
-  constexpr int GM = 8;
-  const int per_group = GM * ntn;
-  const int group = t / per_group, first_m = group * GM;
-  const int gsz = min(ntm - first_m, GM);
-  const int tm = first_m + (t % per_group) % gsz;
-  const int tn = (t % per_group) / gsz;
+  int tm, tn;
+  grouped_tile(xcd_remap(blockIdx.x, ntm * ntn), ntm, ntn, 8, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
 
   // ---- staging addresses: wave w owns LDS-DMA pieces F w .. F w + F - 1 (8 rows x 128 B each) of A and W
@@ -208,8 +189,7 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const T* __restrict__ A, c
 }
 
 // gemm256.hip: 256x256 ping-pong kernel for large M
-int gemm256_launch(const void* A, const void* W, void* C, int M, int N, int K, int epi, const float* bias,
-                   const float* rope, int L, int rope_batch, int hd, int rope_cols, float q_scale, int q_cols, int dtype,
+int gemm256_launch(const void* A, const void* W, void* C, int M, int N, int K, int epi, const GemmEpi& e, int dtype,
                    hipStream_t st, int form = 0);  // 0 shipped choice, 1 one tile per workgroup, 2 persistent prologue form
 int gemm256_cu_count();  // CUs of the device = the persistent kernel's grid
 
@@ -283,8 +263,7 @@ static int launch_gemm(const void* A, const void* W, void* C, int M, int N, int 
   // (profiles/r03_gemm_min_tiles_ab.txt). Shapes of batch >= 4 have 320 tiles or more and are not touched.
   const long tiles256 = (long)((M + 255) / 256) * (N / 256);
   if (can256 && (g_force_tile >= 256 || (g_force_tile == 0 && M >= 4096 && tiles256 >= min_tiles256())))
-    return gemm256_launch(A, W, C, M, N, K, epi, e.bias, e.rope, e.L, e.rope_batch, e.hd, e.rope_cols, e.q_scale, e.q_cols,
-                          dtype_of<T>(), st, g_force_tile == 257 ? 1 : g_force_tile == 258 ? 2 : 0);
+    return gemm256_launch(A, W, C, M, N, K, epi, e, dtype_of<T>(), st, g_force_tile == 257 ? 1 : g_force_tile == 258 ? 2 : 0);
   constexpr int BM = 128, BN = 128;
   int ntm = (M + BM - 1) / BM, ntn = N / BN;
   ProfScope prof(PROF_GEMM_SMALL, 2.0 * M * N * K, st);
@@ -303,22 +282,18 @@ static int launch_gemm(const void* A, const void* W, void* C, int M, int N, int 
     ntm = (M + 63) / 64;
     ntn = N / 64;
     dim3 grid64(ntm * ntn), block(256);
-    switch (epi) {
-      case EPI_NONE: hipLaunchKernelGGL((gemm_kernel<T, EPI_NONE, 2>), grid64, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-      case EPI_GELU: hipLaunchKernelGGL((gemm_kernel<T, EPI_GELU, 2>), grid64, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-      case EPI_SILU: hipLaunchKernelGGL((gemm_kernel<T, EPI_SILU, 2>), grid64, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-      default: return set_error(NOVA_ERR_ARG, "gemm: unknown epilogue %d", epi);
-    }
+    if (int rc = dispatch_epi(epi, [&](auto tag) {
+          constexpr int EPI = decltype(tag)::value;
+          if constexpr (EPI != EPI_ROPE) hipLaunchKernelGGL((gemm_kernel<T, EPI, 2>), grid64, block, 0, st, a, w, c, M, N, K, ntm, ntn, e);
+        }))
+      return rc;
     return check_launch("gemm (64 tile)");
   }
   dim3 grid(ntm * ntn), block(256);
-  switch (epi) {
-    case EPI_NONE: hipLaunchKernelGGL((gemm_kernel<T, EPI_NONE>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    case EPI_GELU: hipLaunchKernelGGL((gemm_kernel<T, EPI_GELU>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    case EPI_SILU: hipLaunchKernelGGL((gemm_kernel<T, EPI_SILU>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    case EPI_ROPE: hipLaunchKernelGGL((gemm_kernel<T, EPI_ROPE>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    default: return set_error(NOVA_ERR_ARG, "gemm: unknown epilogue %d", epi);
-  }
+  if (int rc = dispatch_epi(epi, [&](auto tag) {
+        hipLaunchKernelGGL((gemm_kernel<T, decltype(tag)::value>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e);
+      }))
+    return rc;
   return check_launch("gemm");
 }
 

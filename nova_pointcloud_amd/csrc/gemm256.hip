@@ -36,6 +36,14 @@
 // youngest unit(s) (= all of tile t+1); the first read of tile t+1 happens in the next phase, one barrier later.
 // Epilogue: bias (the accumulators start at it), GELU / SiLU / RoPE pair rotation / q-scale lane-local on the lane's 4
 // consecutive columns, as in gemm.hip. Results are bit-identical to gemm.hip: tests/test_gpu_kernels.py compares them.
+//
+// Where things live. This protocol is written once: TileSrc (the staged tile's addresses, stage = the two LDS-DMA pieces of a unit),
+// Wave256 (accumulators and fragments, read_x / read_y, mma_quadrant, and ktile = the four phases with their eight barriers, which
+// takes each phase's staging segment from the kernel), TileWalk (a persistent workgroup's share of the tile list), load_cs,
+// fresh_lane, start_stagger. The three kernels are three schedules on these pieces: gemm256_kernel (one tile per workgroup; its VAR
+// placements keep a phase loop of its own), gemm256p_kernel (persistent, per-tile prologue; the fp8 path), gemm256c_kernel
+// (persistent, continuous K-stream: the shipped choice). Epilogue codes and descriptor: EPI_* / GemmEpi / dispatch_epi in
+// nova_internal.h, shared with gemm.hip; tile order: grouped_tile / xcd_chunk in common.h.
 #include <type_traits>
 #ifndef NOVA_GEMM_ACT_ROWS
 #define NOVA_GEMM_ACT_ROWS 1  // 0: all activations of a tile, then all its stores (A/B build)
@@ -51,27 +59,17 @@ constexpr int P_KLDS = 2 * P_BUF;   // 128 KiB: two K-tile buffers
 constexpr int P_BIAS = P_KLDS;      // persistent form: the tile's 256 bias values (1 KiB), brought in by LDS-DMA like the operands
 constexpr int P_LDS = P_KLDS + 1024;
 
-struct GemmEpi;  // same POD as gemm.hip (redeclared below to keep the translation units independent)
-struct GemmEpi256 {
-  const float* bias;
-  const float* rope;
-  int L, rope_batch, hd, rope_cols;
-  float q_scale;
-  int q_cols;
+// the epilogue descriptor every GEMM structure takes (nova_internal.h) + the 256 tile's own fields
+struct GemmEpi256 : GemmEpi {
   int gm;  // row panels per tile group (L2 reuse shape)
   int rev;      // persistent form: walk each XCD's chunk of the tile list back to front (xcd_remap_dir, common.h)
   const float* sa;  // fp8 path: per-row dequantisation scale of A [M]
   const float* sw;  // fp8 path: per-row (output column) dequantisation scale of W [N]
-  int stagger;  // persistent form: start delay of the last workgroup in cycles (0 = none), see gemm256p_kernel
+  int stagger;  // persistent form: start delay of the last workgroup in cycles (0 = none), see start_stagger
   int sa_scalar = 0;            // fp8 path: sa points at ONE scale shared by all rows of A (a tensor quantised with a static scale)
-  const float* q8_scale = nullptr;  // E_GELU_Q8: the scale the e4m3 output is quantised with (one float, read at kernel entry)
-  unsigned* q8_amax = nullptr;      // E_GELU_Q8: running max |value| of the un-quantised outputs, as float bits (atomic max)
+  const float* q8_scale = nullptr;  // EPI_GELU_Q8: the scale the e4m3 output is quantised with (one float, read at kernel entry)
+  unsigned* q8_amax = nullptr;      // EPI_GELU_Q8: running max |value| of the un-quantised outputs, as float bits (atomic max)
 };
-
-// E_GELU_Q8 (fp8 operands only): GELU, then the result is written as OCP e4m3 bytes, value / *q8_scale saturated at +-448,
-// instead of bf16 - the A operand of the next fp8 GEMM without a quantisation pass ("delayed scaling": the caller derives
-// the next call's scale from q8_amax).
-enum { E_NONE = 0, E_GELU = 1, E_SILU = 2, E_ROPE = 3, E_GELU_Q8 = 5 };
 
 template <typename T> struct PFrag;
 template <> struct PFrag<bf16_t> { u4v v; };
@@ -130,17 +128,17 @@ template <bool COLS8> __device__ __forceinline__ int col_of(int fr, int xi) { re
 // ROT: pair rotation with the row's table entry t = (cos0, sin0, cos1, sin1) (the two pairs of these 4 columns).
 template <typename OT, int EPI, bool ROT>
 __device__ __forceinline__ f4v epi_apply(f4v v, f4v t, float qmul) {
-  if (EPI == E_GELU) {
+  if (EPI == EPI_GELU) {
     if (sizeof(OT) == 2) {
       v = gelu_erf_fast4(v);
     } else {
 #pragma unroll
       for (int q = 0; q < 4; ++q) v[q] = gelu_erf(v[q]);
     }
-  } else if (EPI == E_SILU) {
+  } else if (EPI == EPI_SILU) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) v[q] = silu(v[q]);
-  } else if (EPI == E_ROPE) {
+  } else if (EPI == EPI_ROPE) {
     if (ROT) v = rope_rotate4(v, t);
     v = v * qmul;  // tile-uniform; x * 1.0f is exact
   }
@@ -172,6 +170,208 @@ __device__ __forceinline__ void store8(OT* dst, f4v lo, f4v hi) {  // 8 consecut
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// What the kernels below share, each defined once: the unit layout and the staging of a unit (TileSrc, all three kernels); for the two
+// persistent forms the fragment reads, the MFMA quadrant and the four-phase K-tile with its eight barriers (Wave256), the RoPE
+// table-row loader, the tile walk and the start stagger. A persistent kernel states only what is its own: which unit each phase
+// requests and where its counted wait sits.
+
+// LDS offset of unit u (staging order: 0 = X(0), 1 = Y(1), 2 = X(1), 3 = Y(0)) inside a K-tile buffer, laid out X(0) X(1) Y(0) Y(1)
+__device__ __forceinline__ int unit_off(int u) { return (u == 0 ? 0 : u == 2 ? 1 : u == 3 ? 2 : 3) * P_UNIT; }
+
+// Persistent forms: lane-derived values (fragment rows, DMA source offsets) are re-derived from an opaque copy of the lane id once
+// per tile and once per epilogue: kept as kernel-lifetime invariants they occupy ~45 VGPRs across the epilogue,
+// which then spills its RoPE table rows.
+__device__ __forceinline__ int fresh_lane(int lane) {
+  asm volatile("" : "+v"(lane));
+  return lane;
+}
+
+// Persistent forms: phase-shift the workgroups so that their epilogue store bursts do not coincide chip-wide (`cycles` = start
+// delay of the last workgroup, 0 = none)
+__device__ __forceinline__ void start_stagger(int cycles) {
+  if (cycles > 0) {
+    const long long until = clock64() + (long long)cycles * (int)blockIdx.x / (int)gridDim.x;
+    while (clock64() < until) __builtin_amdgcn_s_sleep(8);
+  }
+}
+
+// Persistent forms: this workgroup's share of the tile list. XCD x = blockIdx % 8 owns one contiguous chunk (xcd_remap's split,
+// common.h), its gridDim/8 workgroups take that chunk's tiles round-robin: steps first(), first() + nslot, ... while has(step);
+// back to front when e.rev is set (xcd_remap_dir). Same tile order as the one-tile-per-workgroup launch.
+struct TileWalk {
+  int cbase, csize, nslot, ntm, ntn, gm, rev;
+  __device__ __forceinline__ TileWalk(int ntm_, int ntn_, const GemmEpi256& e)
+      : nslot(gridDim.x >> 3), ntm(ntm_), ntn(ntn_), gm(e.gm), rev(e.rev) {
+    xcd_chunk(blockIdx.x & 7, ntm * ntn, cbase, csize);
+  }
+  __device__ __forceinline__ int first() const { return blockIdx.x >> 3; }
+  __device__ __forceinline__ bool has(int step) const { return step < csize; }
+  __device__ __forceinline__ void origin(int step, int& m0, int& n0) const {
+    int tm, tn;
+    grouped_tile(cbase + (rev ? csize - 1 - step : step), ntm, ntn, gm, tm, tn);
+    m0 = tm * 256;
+    n0 = tn * 256;
+  }
+};
+
+// Persistent forms, RoPE through registers: the table rows of a lane's 16 output rows (tile rows row0 + 16 y + 4 fg + r) for its 4
+// columns from tile column `col`: cs[y][r] = (cos0, sin0, cos1, sin1) of the two pairs in those columns.
+__device__ __forceinline__ void load_cs(const GemmEpi256& e, int M, int row0, int fg, int col, f4v (&cs)[4][4]) {
+  const int tcol = col % e.hd;
+#pragma unroll
+  for (int y = 0; y < 4; ++y) {
+    // (sequence, position) of the fragment's first row on wave-uniform values, the lane's rows by increment
+    const int mb = min(__builtin_amdgcn_readfirstlane(row0 + y * 16), M - 1);
+    const int s0 = mb / e.L, l0 = mb - s0 * e.L;
+    const int b0 = s0 % e.rope_batch, b1 = b0 + 1 == e.rope_batch ? 0 : b0 + 1;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      int l = l0 + min(fg * 4 + r, M - 1 - mb);  // rows past M reuse row M-1 (never stored differently)
+      int sb = b0;
+      if (l >= e.L) { l -= e.L; sb = b1; }  // a 16-row block crosses at most one sequence boundary (L >= 16)
+      cs[y][r] = *reinterpret_cast<const f4v*>(e.rope + ((size_t)sb * e.L + l) * e.hd + tcol);
+    }
+  }
+}
+
+// The tile a wave is STAGING: wave-uniform tile bases + per-lane 32-bit byte offsets - the LDS-DMA instructions then take an SGPR base
+// and a 32-bit VGPR offset, and advancing along K is scalar arithmetic (no 64-bit vector add per issue). (A struct of its own and
+// not part of Wave256: held beside the accumulators, the fp8 prologue form spills more - profiles/gemm256_shared_codegen.txt.)
+template <typename T>
+struct TileSrc {
+  const char *a_base, *w_base;
+  uint32_t soff[4][2];
+  template <bool COLS8>
+  __device__ __forceinline__ void set(const T* A, const T* W, int m0, int n0, int M, int K, int lane, int wid) {
+    const size_t rowbytes = (size_t)K * sizeof(T);
+    a_base = reinterpret_cast<const char*>(A) + (size_t)m0 * rowbytes;
+    w_base = reinterpret_cast<const char*>(W) + (size_t)n0 * rowbytes;
+    dma_offsets<COLS8>(lane, wid, M - 1 - m0, (uint32_t)rowbytes, soff);
+  }
+  // unit u of K-tile kt: all 8 waves, 2 LDS-DMA instructions (pieces) each
+  // (the `nt` policy on either operand's staging loads loses 3-10 %: profiles/r04_gemm_nt_stores_ab.txt)
+  __device__ __forceinline__ void stage(char* smem, int wid, int u, int kt) const {
+    char* dst = smem + (kt & 1) * P_BUF + unit_off(u) + wid * 2048;
+    const char* base = ((u == 0 || u == 2) ? w_base : a_base) + (size_t)kt * 128;
+    __builtin_amdgcn_global_load_lds(base + soff[u][0], NOVA_LDS_PTR(dst), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(base + soff[u][1], NOVA_LDS_PTR(dst + 1024), 16, 0, 0);
+  }
+  __device__ __forceinline__ void stage_piece(char* smem, int wid, int u, int kt, int i) const {  // (one-tile kernel, VAR 1)
+    char* dst = smem + (kt & 1) * P_BUF + unit_off(u) + wid * 2048 + i * 1024;
+    const char* base = ((u == 0 || u == 2) ? w_base : a_base) + (size_t)kt * 128;
+    __builtin_amdgcn_global_load_lds(base + soff[u][i], NOVA_LDS_PTR(dst), 16, 0, 0);
+  }
+};
+
+// Persistent forms: per-wave compute state of a 256 x 256 tile and the steps of the K loop (header comment: operand roles and phase plan).
+template <typename T>
+struct Wave256 {
+  static constexpr bool FP8 = sizeof(T) == 1;
+  char* const smem;
+  const int wid, wr, wc;  // wave-uniform: the wave, its group (= column half of the tile) and its 64-row block
+  int fr, fg;             // fragment row lane & 15 and k chunk lane >> 4 (set_lane)
+  f4v acc[4][8];  // [y fragment][x fragment]
+  f4v bcol[2];    // the bias of the lane's columns: every accumulator of X fragment (xi, f) holds column col_of(fr, xi) + f
+  PFrag<T> xf[4][2], yf0[2][2], yf1[2][2];
+
+  __device__ __forceinline__ Wave256(char* smem_, int wid_) : smem(smem_), wid(wid_), wr(wid_ >> 2), wc(wid_ & 3) {}
+  __device__ __forceinline__ void set_lane(int lane) { fr = lane & 15; fg = lane >> 4; }
+
+  // Persistent forms: a tile's 256 bias values -> LDS by wave 0, like the operands; requested ahead of (= older than) the tile's first
+  // units, so landed when the wait for those returns (in-order retirement) and visible to all waves after that wait's barrier
+  __device__ __forceinline__ void stage_bias(const float* bias, int n0, int lane) const {
+    if (wid == 0) __builtin_amdgcn_global_load_lds(reinterpret_cast<const char*>(bias + n0) + lane * 16, NOVA_LDS_PTR(smem + P_BIAS), 16, 0, 0);
+  }
+  template <bool COLS8>
+  __device__ __forceinline__ void read_bias(bool lds_bias) {
+#pragma unroll
+    for (int xi = 0; xi < 2; ++xi)
+      bcol[xi] = lds_bias ? *reinterpret_cast<const f4v*>(smem + P_BIAS + (wr * 128 + col_of<COLS8>(fr, xi)) * 4) : f4v{0.f, 0.f, 0.f, 0.f};
+  }
+
+  __device__ __forceinline__ void read_x(const char* buf, int xi) {
+    const char* u = buf + xi * P_UNIT;
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) xf[f][kk] = punit_frag<T>(u, wr * 64 + f * 16 + fr, fg + 4 * kk);
+  }
+  __device__ __forceinline__ void read_y(const char* buf, int yi, PFrag<T> (&yf)[2][2]) {
+    const char* u = buf + (2 + yi) * P_UNIT;
+#pragma unroll
+    for (int f = 0; f < 2; ++f)
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) yf[f][kk] = punit_frag<T>(u, wc * 32 + f * 16 + fr, fg + 4 * kk);
+  }
+  // 16 MFMAs of one quadrant. FIRST (the tile's first K-tile, persistent forms): the accumulators start at the bias - the first MFMA
+  // of every accumulator (k half 0) takes the bias of its column (bcol), splat over the lane's 4 rows, as its C operand, so there is
+  // neither a zeroing pass nor a bias add in the epilogue.
+  template <bool FIRST>
+  __device__ __forceinline__ void mma_quadrant(int xi, int yi, PFrag<T> (&yf)[2][2]) {
+    f4v c0[4];
+    if constexpr (FIRST) {
+#pragma unroll
+      for (int x = 0; x < 4; ++x) c0[x] = f4v{bcol[xi][x], bcol[xi][x], bcol[xi][x], bcol[xi][x]};
+    }
+    __builtin_amdgcn_s_setprio(1);
+    if constexpr (FP8) {
+      // MX-fp8: ONE v_mfma_scale_f32_16x16x128_f8f6f4 per accumulator and K-tile (twice the bf16 rate). A lane's 32 operand
+      // bytes are the two 16-byte chunks (fg, fg + 4) it reads anyway - the same (lane, byte) -> k map on both operands,
+      // which is all a contraction needs. Block scales are 1 (e8m0 127); the per-row scales are applied in the epilogue.
+#pragma unroll
+      for (int f = 0; f < 2; ++f)
+#pragma unroll
+        for (int x = 0; x < 4; ++x) {
+          const i8v yv = __builtin_bit_cast(i8v, __builtin_shufflevector(yf[f][0].v, yf[f][1].v, 0, 1, 2, 3, 4, 5, 6, 7));
+          const i8v xv = __builtin_bit_cast(i8v, __builtin_shufflevector(xf[x][0].v, xf[x][1].v, 0, 1, 2, 3, 4, 5, 6, 7));
+          acc[yi * 2 + f][xi * 4 + x] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
+              yv, xv, FIRST ? c0[x] : acc[yi * 2 + f][xi * 4 + x], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+        }
+    } else {
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int f = 0; f < 2; ++f)
+#pragma unroll
+          for (int x = 0; x < 4; ++x)
+            acc[yi * 2 + f][xi * 4 + x] = pmma(yf[f][kk], xf[x][kk], (FIRST && kk == 0) ? c0[x] : acc[yi * 2 + f][xi * 4 + x]);
+    }
+    __builtin_amdgcn_s_setprio(0);
+  }
+  // One K-tile of the persistent forms = 4 phases (header comment): the fragment reads, the eight barriers and the quadrant order.
+  // s0 .. s3 are the phases' staging segments, which is where the forms differ; s3 also holds the K-tile's counted wait.
+  template <bool FIRST, typename S0, typename S1, typename S2, typename S3>
+  __device__ __forceinline__ void ktile(int kt, S0&& s0, S1&& s1, S2&& s2, S3&& s3) {
+    const char* buf = smem + (kt & 1) * P_BUF;
+    read_x(buf, 0);
+    read_y(buf, 0, yf0);
+    s0();
+    NOVA_BARRIER();
+    mma_quadrant<FIRST>(0, 0, yf0);
+    NOVA_BARRIER();
+    read_y(buf, 1, yf1);
+    s1();
+    NOVA_BARRIER();
+    mma_quadrant<FIRST>(0, 1, yf1);
+    NOVA_BARRIER();
+    read_x(buf, 1);
+    s2();
+    NOVA_BARRIER();
+    mma_quadrant<FIRST>(1, 1, yf1);
+    NOVA_BARRIER();
+    s3();  // no LDS reads: quadrant (1,0) runs on the Y(0) fragments held since phase 0
+    NOVA_BARRIER();
+    mma_quadrant<FIRST>(1, 0, yf0);
+    NOVA_BARRIER();
+  }
+  // 4 consecutive columns of output row (y, r): component r of 4 accumulators. The packing instruction takes any two registers, so
+  // nothing has to be moved together first.
+  __device__ __forceinline__ f4v value4(int y, int r, int xi) const {
+    return f4v{acc[y][xi * 4][r], acc[y][xi * 4 + 1][r], acc[y][xi * 4 + 2][r], acc[y][xi * 4 + 3][r]};
+  }
+};
+
 // VAR selects where the two LDS-DMA instructions of a phase are issued (A/B-tested on the GPU, tools/microbench.py):
 //   0: both between the two k-halves of the MFMA segment   1: one in the load segment, one in the MFMA segment
 //   2: both in the load segment after the fragment reads   3: both in the load segment before the fragment reads
@@ -187,33 +387,18 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const T* __restrict__ A
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wid >> 2, wc = wid & 3;
 
-  const int nwg = ntm * ntn;
-  const int t = xcd_remap(blockIdx.x, nwg);
-  const int GM = e.gm;
-  const int per_group = GM * ntn;
-  const int group = t / per_group, first_m = group * GM;
-  const int gsz = min(ntm - first_m, GM);
-  const int tm = first_m + (t % per_group) % gsz;
-  const int tn = (t % per_group) / gsz;
+  int tm, tn;
+  grouped_tile(xcd_remap(blockIdx.x, ntm * ntn), ntm, ntn, e.gm, tm, tn);
   const int m0 = tm * 256, n0 = tn * 256;
 
   // wave-uniform tile bases + per-lane 32-bit byte offsets: the LDS-DMA instructions then take an SGPR base and a
   // 32-bit VGPR offset, and advancing along K is scalar arithmetic (no 64-bit vector add per issue)
-  const size_t rowbytes = (size_t)K * sizeof(T);
-  const char* a_base = reinterpret_cast<const char*>(A) + (size_t)m0 * rowbytes;
-  const char* w_base = reinterpret_cast<const char*>(W) + (size_t)n0 * rowbytes;
-  constexpr bool COLS8 = EPI != E_ROPE;  // column map of the X fragments (header comment)
-  uint32_t soff[4][2];
-  dma_offsets<COLS8>(lane, wid, M - 1 - m0, (uint32_t)rowbytes, soff);
+  constexpr bool COLS8 = EPI != EPI_ROPE;  // column map of the X fragments (header comment)
+  TileSrc<T> src;
+  src.template set<COLS8>(A, W, m0, n0, M, K, lane, wid);
   const int nkt = K / (128 / (int)sizeof(T));
-  // LDS offset of unit u inside a buffer: X(0) X(1) Y(0) Y(1)
-  auto unit_off = [](int u) { return (u == 0 ? 0 : u == 2 ? 1 : u == 3 ? 2 : 3) * P_UNIT; };
   auto stage_piece = [&](int u, int kt, int i) {
-    if (kt < nkt) {
-      char* dst = smem + (kt & 1) * P_BUF + unit_off(u) + wid * 2048 + i * 1024;
-      const char* base = ((u == 0 || u == 2) ? w_base : a_base) + (size_t)kt * 128;
-      __builtin_amdgcn_global_load_lds(base + soff[u][i], NOVA_LDS_PTR(dst), 16, 0, 0);
-    }
+    if (kt < nkt) src.stage_piece(smem, wid, u, kt, i);
   };
   auto stage = [&](int u, int kt) {  // all 8 waves: 2 LDS-DMA instructions each (wave-uniform condition)
     if (VAR >= 10 && kt >= 2) return;  // ablation builds (timing only, wrong results): no prefetch inside the loop
@@ -245,6 +430,9 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const T* __restrict__ A
   NOVA_BARRIER();
   if (wr == 1) NOVA_BARRIER();  // group 1 runs one barrier behind group 0 from here on
 
+  // The fragment reads, the quadrant and the four phases are this kernel's own copies of Wave256's: they carry the VAR placements and
+  // ablation guards, and with its accumulators and fragments held in a Wave256 the VAR >= 10 instantiations take 2-3 more VGPRs
+  // (profiles/gemm256_shared_codegen.txt).
   PFrag<T> xf[4][2], yf0[2][2], yf1[2][2];
   auto read_x = [&](const char* buf, int xi) {
     if (VAR >= 11 && buf != smem) return;
@@ -330,8 +518,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const T* __restrict__ A
   if (wr == 0) NOVA_BARRIER();  // re-align the groups
 
   // ---- epilogue (lane-local): the lane holds out[rows 4 fg + r of Y fragment y][columns col_of(fr, xi) + {0..3}]
-  const bool rot = EPI == E_ROPE && n0 < e.rope_cols;
-  const float qmul = (EPI == E_ROPE && n0 < e.q_cols) ? e.q_scale : 1.0f;
+  const bool rot = EPI == EPI_ROPE && n0 < e.rope_cols;
+  const float qmul = (EPI == EPI_ROPE && n0 < e.q_cols) ? e.q_scale : 1.0f;
   const int nw = n0 + wr * 128;
 #pragma unroll
   for (int y = 0; y < 4; ++y) {
@@ -405,8 +593,8 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const T* __restrict__ 
                                                           int ntm, int ntn, GemmEpi256 e) {
   typedef typename OutOf<T>::type OT;
   constexpr bool FP8 = sizeof(T) == 1;
-  constexpr bool Q8 = EPI == E_GELU_Q8;
-  constexpr bool COLS8 = EPI != E_ROPE;  // column map of the X fragments (header comment)
+  constexpr bool Q8 = EPI == EPI_GELU_Q8;
+  constexpr bool COLS8 = EPI != EPI_ROPE;  // column map of the X fragments (header comment)
   // vector-memory operations a wave issues per tile epilogue behind the next tile's prologue DMAs (exact: the wait at the next
   // tile top counts them): one store per output row and 16 bytes = 16 for 16-bit results with the 8-column map, 32 with the
   // 4-column map and for f32 results; e4m3 results: 16 8-byte stores + 1 atomic max
@@ -414,157 +602,46 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const T* __restrict__ 
   __shared__ __attribute__((aligned(16))) char smem[P_LDS + P_STAMPS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wid >> 2, wc = wid & 3;
+  Wave256<T> w(smem, wid);
+  const int wr = w.wr, wc = w.wc;
   [[maybe_unused]] int stamp_tile = 0;
 
-  // this workgroup's share of the tile list: XCD x = blockIdx % 8 owns one contiguous chunk (xcd_remap's
-  // split), its gridDim/8 workgroups take that chunk's tiles round-robin
-  const int nwg = ntm * ntn;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
-  const int cq = nwg >> 3, cr = nwg & 7;
-  const int cbase = xcd < cr ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq;
-  const int csize = cq + (xcd < cr ? 1 : 0);
-  if (slot >= csize) return;  // workgroup-uniform, before any barrier
+  const TileWalk walk(ntm, ntn, e);
+  if (!walk.has(walk.first())) return;  // workgroup-uniform, before any barrier
 
-  const int GM = e.gm;
-  const int per_group = GM * ntn;
-  auto tile_origin = [&](int t, int& m0, int& n0) {
-    const int group = t / per_group, first_m = group * GM;
-    const int gsz = min(ntm - first_m, GM);
-    m0 = (first_m + (t % per_group) % gsz) * 256;
-    n0 = ((t % per_group) / gsz) * 256;
-  };
-
-  // Lane-derived values (fragment rows, DMA source offsets) are re-derived from an opaque copy of the lane id once
-  // per tile and once per epilogue: kept as kernel-lifetime invariants they occupy ~45 VGPRs across the epilogue,
-  // which then spills its RoPE table rows.
-  auto fresh_lane = [&]() { int l = lane; asm volatile("" : "+v"(l)); return l; };
-  const size_t rowbytes = (size_t)K * sizeof(T);
-  const char *a_base, *w_base;
-  uint32_t soff[4][2];
-  auto set_tile = [&](int m0, int n0) {
-    a_base = reinterpret_cast<const char*>(A) + (size_t)m0 * rowbytes;
-    w_base = reinterpret_cast<const char*>(W) + (size_t)n0 * rowbytes;
-    dma_offsets<COLS8>(fresh_lane(), wid, M - 1 - m0, (uint32_t)rowbytes, soff);
-  };
   const int nkt = K / (128 / (int)sizeof(T));
-  auto unit_off = [](int u) { return (u == 0 ? 0 : u == 2 ? 1 : u == 3 ? 2 : 3) * P_UNIT; };
+  TileSrc<T> src;
   auto stage = [&](int u, int kt) {
-    if (kt < nkt) {
-      char* dst = smem + (kt & 1) * P_BUF + unit_off(u) + wid * 2048;
-      const char* base = ((u == 0 || u == 2) ? w_base : a_base) + (size_t)kt * 128;
-      __builtin_amdgcn_global_load_lds(base + soff[u][0], NOVA_LDS_PTR(dst), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(base + soff[u][1], NOVA_LDS_PTR(dst + 1024), 16, 0, 0);
-    }
+    if (kt < nkt) src.stage(smem, wid, u, kt);
   };
   const bool lds_bias = !FP8 && e.bias != nullptr;  // fp8: accumulators start at zero, the scales multiply the raw sums (bias added in the epilogue)
-  // the tile's 256 bias values -> LDS, by wave 0, ahead of (= older than) the prologue units: landed when the wait at the tile top
-  // returns (in-order retirement) and visible to all waves after that wait's barrier
-  auto stage_prologue = [&](int n0) {
-    if (lds_bias && wid == 0)
-      __builtin_amdgcn_global_load_lds(reinterpret_cast<const char*>(e.bias + n0) + lane * 16, NOVA_LDS_PTR(smem + P_BIAS), 16, 0, 0);
+  // a tile's bias + its first six units, in that order (the bias is read from LDS after the wait + barrier at the tile top)
+  auto stage_prologue = [&](int m0, int n0) {
+    src.template set<COLS8>(A, W, m0, n0, M, K, fresh_lane(lane), wid);
+    if (lds_bias) w.stage_bias(e.bias, n0, lane);
     stage(0, 0); stage(1, 0); stage(2, 0); stage(3, 0);
     stage(0, 1); stage(1, 1);
   };
-
-  int fr, fg;
-  f4v acc[4][8];  // [y fragment][x fragment]
-  PFrag<T> xf[4][2], yf0[2][2], yf1[2][2];
-  auto read_x = [&](const char* buf, int xi) {
-    const char* u = buf + xi * P_UNIT;
-#pragma unroll
-    for (int f = 0; f < 4; ++f)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) xf[f][kk] = punit_frag<T>(u, wr * 64 + f * 16 + fr, fg + 4 * kk);
-  };
-  auto read_y = [&](const char* buf, int yi, PFrag<T> (&yf)[2][2]) {
-    const char* u = buf + (2 + yi) * P_UNIT;
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) yf[f][kk] = punit_frag<T>(u, wc * 32 + f * 16 + fr, fg + 4 * kk);
-  };
-  // The accumulators start at the bias: the first MFMA of every accumulator (k half 0 of the tile's first K-tile) takes
-  // the bias of its column, splat over the lane's 4 rows, as its C operand, so there is neither a zeroing pass nor a bias
-  // add in the epilogue.
-  f4v bcol[2];
-  auto mma_quadrant = [&](int xi, int yi, PFrag<T> (&yf)[2][2], auto first_ktile) {
-    constexpr bool FIRST = decltype(first_ktile)::value;
-    f4v c0[4];
-    if constexpr (FIRST) {
-#pragma unroll
-      for (int x = 0; x < 4; ++x) c0[x] = f4v{bcol[xi][x], bcol[xi][x], bcol[xi][x], bcol[xi][x]};
-    }
-    __builtin_amdgcn_s_setprio(1);
-    if constexpr (FP8) {
-      // MX-fp8: ONE v_mfma_scale_f32_16x16x128_f8f6f4 per accumulator and K-tile (twice the bf16 rate). A lane's 32 operand
-      // bytes are the two 16-byte chunks (fg, fg + 4) it reads anyway - the same (lane, byte) -> k map on both operands,
-      // which is all a contraction needs. Block scales are 1 (e8m0 127); the per-row scales are applied in the epilogue.
-#pragma unroll
-      for (int f = 0; f < 2; ++f)
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-          const i8v yv = __builtin_bit_cast(i8v, __builtin_shufflevector(yf[f][0].v, yf[f][1].v, 0, 1, 2, 3, 4, 5, 6, 7));
-          const i8v xv = __builtin_bit_cast(i8v, __builtin_shufflevector(xf[x][0].v, xf[x][1].v, 0, 1, 2, 3, 4, 5, 6, 7));
-          acc[yi * 2 + f][xi * 4 + x] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-              yv, xv, FIRST ? c0[x] : acc[yi * 2 + f][xi * 4 + x], 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
-        }
-    } else {
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-        for (int f = 0; f < 2; ++f)
-#pragma unroll
-          for (int x = 0; x < 4; ++x)
-            acc[yi * 2 + f][xi * 4 + x] = pmma(yf[f][kk], xf[x][kk], (FIRST && kk == 0) ? c0[x] : acc[yi * 2 + f][xi * 4 + x]);
-    }
-    __builtin_amdgcn_s_setprio(0);
-  };
-  auto read_bias = [&]() {  // after the tile-top wait + barrier
-#pragma unroll
-    for (int xi = 0; xi < 2; ++xi)
-      bcol[xi] = lds_bias ? *reinterpret_cast<const f4v*>(smem + P_BIAS + (wr * 128 + col_of<COLS8>(fr, xi)) * 4) : f4v{0.f, 0.f, 0.f, 0.f};
-  };
-  // one K-tile: 4 phases (see the header comment)
+  // one K-tile: each phase requests the unit 6 ahead in the tile's own sequence (nothing past its last K-tile); the wait retires
+  // all but the youngest unit(s), everything on the last two K-tiles
   auto ktile = [&](int kt, auto first_ktile) {
-    const char* buf = smem + (kt & 1) * P_BUF;
-    read_x(buf, 0);
-    read_y(buf, 0, yf0);
-    stage(2, kt + 1);
-    NOVA_BARRIER();
-    mma_quadrant(0, 0, yf0, first_ktile);
-    NOVA_BARRIER();
-    read_y(buf, 1, yf1);
-    stage(3, kt + 1);
-    NOVA_BARRIER();
-    mma_quadrant(0, 1, yf1, first_ktile);
-    NOVA_BARRIER();
-    read_x(buf, 1);
-    stage(0, kt + 2);
-    NOVA_BARRIER();
-    mma_quadrant(1, 1, yf1, first_ktile);
-    NOVA_BARRIER();
-    stage(1, kt + 2);
-    if (kt + 2 < nkt) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    NOVA_BARRIER();
-    mma_quadrant(1, 0, yf0, first_ktile);
-    NOVA_BARRIER();
+    w.template ktile<decltype(first_ktile)::value>(
+        kt, [&] { stage(2, kt + 1); }, [&] { stage(3, kt + 1); }, [&] { stage(0, kt + 2); },
+        [&] {
+          stage(1, kt + 2);
+          if (kt + 2 < nkt) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+          else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        });
   };
 
-  if (e.stagger > 0) {  // phase-shift the workgroups so that their epilogue store bursts do not coincide chip-wide
-    const long long until = clock64() + (long long)e.stagger * (int)blockIdx.x / (int)gridDim.x;
-    while (clock64() < until) __builtin_amdgcn_s_sleep(8);
-  }
+  start_stagger(e.stagger);
   int m0, n0;
-  int it = slot;
-  auto tile_at = [&](int i) { return cbase + (e.rev ? csize - 1 - i : i); };
-  tile_origin(tile_at(it), m0, n0);
-  set_tile(m0, n0);
-  stage_prologue(n0);
+  int it = walk.first();
+  walk.origin(it, m0, n0);
+  stage_prologue(m0, n0);
   bool first = true;
   for (;;) {
-    { const int l = fresh_lane(); fr = l & 15; fg = l >> 4; }
+    w.set_lane(fresh_lane(lane));
     NOVA_STAMP(0);
     // K-tile 0 of this tile (and its bias) landed: all but (tile 1: X0, Y1) and, after the first tile, everything the previous
     // epilogue issued after the prologue DMAs (its STORES_TILE stores)
@@ -574,7 +651,7 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const T* __restrict__ 
     NOVA_BARRIER();
     if (wr == 1) NOVA_BARRIER();  // group 1 runs one barrier behind group 0 inside the K loop
     NOVA_STAMP(1);
-    read_bias();
+    w.template read_bias<COLS8>(lds_bias);
     ktile(0, std::true_type{});
     NOVA_STAMP(2);
     for (int kt = 1; kt < nkt - 1; ++kt) ktile(kt, std::false_type{});
@@ -589,9 +666,11 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const T* __restrict__ 
     // results are spilled around it)
     int cm0 = m0, cn0 = n0;
     asm volatile("" : "+s"(cm0), "+s"(cn0));
-    { const int l = fresh_lane(); fr = l & 15; fg = l >> 4; }
-    const bool rot = EPI == E_ROPE && cn0 < e.rope_cols;
-    const float qmul = (EPI == E_ROPE && cn0 < e.q_cols) ? e.q_scale : 1.0f;  // tile-uniform; x * 1.0f is exact
+    w.set_lane(fresh_lane(lane));
+    const int fr = w.fr, fg = w.fg;
+    auto& acc = w.acc;
+    const bool rot = EPI == EPI_ROPE && cn0 < e.rope_cols;
+    const float qmul = (EPI == EPI_ROPE && cn0 < e.q_cols) ? e.q_scale : 1.0f;  // tile-uniform; x * 1.0f is exact
     const int nw = cn0 + wr * 128;  // the wave's first column; the lane's 4 columns of half xi start at nw + col_of(fr, xi)
     // fp8: out = acc * sa[row] * sw[col] + bias[col]; the three vectors are requested first and consumed before the DMAs
     if constexpr (FP8) {
@@ -617,43 +696,27 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const T* __restrict__ 
     // (head_dim 96) the table rows of half 1 are loaded after half 0 is done.
     f4v cs[4][4];  // [y fragment][r]
     const bool same_cols = 64 % e.hd == 0;
-    auto load_cs = [&](int xi) {
-      const int tcol = (nw + col_of<COLS8>(fr, xi)) % e.hd;
-#pragma unroll
-      for (int y = 0; y < 4; ++y) {
-        // (sequence, position) of the fragment's first row on wave-uniform values, the lane's rows by increment
-        const int mb = min(__builtin_amdgcn_readfirstlane(cm0 + wc * 64 + y * 16), M - 1);
-        const int s0 = mb / e.L, l0 = mb - s0 * e.L;
-        const int b0 = s0 % e.rope_batch, b1 = b0 + 1 == e.rope_batch ? 0 : b0 + 1;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          int l = l0 + min(fg * 4 + r, M - 1 - mb);  // rows past M reuse row M-1 (never stored differently)
-          int sb = b0;
-          if (l >= e.L) { l -= e.L; sb = b1; }  // a 16-row block crosses at most one sequence boundary (L >= 16)
-          cs[y][r] = *reinterpret_cast<const f4v*>(e.rope + ((size_t)sb * e.L + l) * e.hd + tcol);
-        }
-      }
-    };
     float q8_inv = 1.0f, q8_max = 0.f;
     if constexpr (Q8) q8_inv = 1.0f / *e.q8_scale;
     // rows past M were staged as copies of row M-1, so their lanes hold row M-1's results and store the identical
     // bytes there again: no branch, and every tile issues the same number of stores (the vmcnt count above)
+    // (a 64-bit product per row, where the continuous form adds a 32-bit row offset to a tile base: with that form here
+    // gemm256p_kernel<fp8, SiLU> goes from 41 to 56 spilled VGPRs - profiles/gemm256_shared_codegen.txt)
     auto row_of = [&](int y, int r) { return min(cm0 + wc * 64 + y * 16 + fg * 4 + r, M - 1); };
-    auto value4 = [&](int y, int r, int xi) { return f4v{acc[y][xi * 4][r], acc[y][xi * 4 + 1][r], acc[y][xi * 4 + 2][r], acc[y][xi * 4 + 3][r]}; };
     auto finish_half = [&](int xi, auto rotated) {  // COLS4: the lane's 4 columns of half xi, all 16 rows
       constexpr bool ROT = decltype(rotated)::value;
 #pragma unroll
       for (int y = 0; y < 4; ++y)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          store4<OT>(C + (size_t)row_of(y, r) * N + nw + col_of<false>(fr, xi), epi_apply<OT, EPI, ROT>(value4(y, r, xi), cs[y][r], qmul));
+          store4<OT>(C + (size_t)row_of(y, r) * N + nw + col_of<false>(fr, xi), epi_apply<OT, EPI, ROT>(w.value4(y, r, xi), cs[y][r], qmul));
     };
     auto finish_rows = [&]() {  // COLS8: the lane's 8 consecutive columns, all 16 rows
 #pragma unroll
       for (int y = 0; y < 4; ++y)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          f4v lo = value4(y, r, 0), hi = value4(y, r, 1);
+          f4v lo = w.value4(y, r, 0), hi = w.value4(y, r, 1);
           if constexpr (Q8) {
             lo = gelu_erf_fast4(lo);
             hi = gelu_erf_fast4(hi);
@@ -677,25 +740,22 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const T* __restrict__ 
     };
     // the next tile's origin, then its prologue (bias + six units) ahead of this tile's stores in the memory pipeline
     // (issued behind them the DMAs queue for thousands of cycles)
-    const int nxt = it + nslot;
-    const bool more = nxt < csize;
-    if (more) tile_origin(tile_at(nxt), m0, n0);
+    const int nxt = it + walk.nslot;
+    const bool more = walk.has(nxt);
+    if (more) walk.origin(nxt, m0, n0);
     auto next_prologue = [&]() {
-      if (more) {
-        set_tile(m0, n0);
-        stage_prologue(n0);
-      }
+      if (more) stage_prologue(m0, n0);
       NOVA_STAMP(6);
     };
     if constexpr (COLS8) {
       next_prologue();
       finish_rows();
     } else if (rot) {  // the rotation is tile-uniform (decided per 256-column tile): two straight-line epilogues behind one scalar branch
-      load_cs(0);
+      load_cs(e, M, cm0 + wc * 64, fg, nw + col_of<COLS8>(fr, 0), cs);
       asm volatile("" ::"v"(cs[3][3]));  // the compiler's wait for the table rows sits here, ahead of the DMAs (loads retire in order)
       next_prologue();
       finish_half(0, std::true_type{});
-      if (!same_cols) load_cs(1);  // (waits for everything in flight: head widths that do not divide 64 only)
+      if (!same_cols) load_cs(e, M, cm0 + wc * 64, fg, nw + col_of<COLS8>(fr, 1), cs);  // (waits for everything in flight: head widths that do not divide 64 only)
       finish_half(1, std::true_type{});
     } else {
       next_prologue();
@@ -704,7 +764,7 @@ __global__ __launch_bounds__(512, 2) void gemm256p_kernel(const T* __restrict__ 
     }
     if constexpr (Q8) {  // one atomic max per wave and tile (values are >= 0: float order == unsigned order of the bits)
       q8_max = wave_max(q8_max);
-      if (fresh_lane() == 0) __hip_atomic_fetch_max(e.q8_amax, __float_as_uint(q8_max), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (fresh_lane(lane) == 0) __hip_atomic_fetch_max(e.q8_amax, __float_as_uint(q8_max), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     NOVA_STAMP(7);
 #ifdef NOVA_STAMPS
@@ -742,7 +802,7 @@ template <typename T, int EPI, bool TDMA = false>
 __global__ __launch_bounds__(512, 2) void gemm256c_kernel(const T* __restrict__ A, const T* __restrict__ W, T* __restrict__ C, int M,
                                                           int N, int K, int ntm, int ntn, GemmEpi256 e) {
   typedef T OT;
-  static_assert(!TDMA || EPI == E_ROPE, "the table-through-LDS form belongs to the RoPE epilogue");
+  static_assert(!TDMA || EPI == EPI_ROPE, "the table-through-LDS form belongs to the RoPE epilogue");
   // TDMA (RoPE, head width 64): the cos / sin rows come through LDS - each wave brings the 16 table rows of one Y fragment
   // (16 x 256 B) into a window of its own by LDS-DMA, one fragment ahead of the one it is rotating, and reads them back with
   // ds_read_b128. Through registers the rows are 16-32 global loads per lane and tile at ~75 cycles of the CU's memory pipeline
@@ -750,81 +810,36 @@ __global__ __launch_bounds__(512, 2) void gemm256c_kernel(const T* __restrict__ 
   // GEMM once the prologue is out of it; an LDS-DMA instruction moves the same kilobyte in 21-33. The windows take the 32 KiB
   // beside the K-tile buffers (so the bias travels in registers in this form) and, since the table is read from LDS, the lane
   // can hold 8 consecutive columns (16-byte stores) like every other epilogue.
-  constexpr bool COLS8 = EPI != E_ROPE || TDMA;  // column map of the X fragments (header comment)
+  constexpr bool COLS8 = EPI != EPI_ROPE || TDMA;  // column map of the X fragments (header comment)
   constexpr int P_TAB = P_KLDS;                   // TDMA: 8 wave windows of 4 KiB
   __shared__ __attribute__((aligned(16))) char smem[TDMA ? P_KLDS + 8 * 4096 : P_LDS + P_STAMPS];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wid >> 2, wc = wid & 3;
+  Wave256<T> w(smem, wid);
+  TileSrc<T> src;  // the tile being computed until the switch in the second-to-last K-tile, the next one after it
+  const int wr = w.wr, wc = w.wc;
   [[maybe_unused]] int stamp_tile = TDMA ? 1 << 20 : 0;  // (no stamp record in the TDMA form: its LDS is full)
 
-  const int nwg = ntm * ntn;
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, nslot = gridDim.x >> 3;
-  const int cq = nwg >> 3, cr = nwg & 7;
-  const int cbase = xcd < cr ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq;
-  const int csize = cq + (xcd < cr ? 1 : 0);
-  if (slot >= csize) return;  // workgroup-uniform, before any barrier
+  const TileWalk walk(ntm, ntn, e);
+  if (!walk.has(walk.first())) return;  // workgroup-uniform, before any barrier
 
 #ifdef NOVA_CLOCK
   const long long ck_t0 = __builtin_amdgcn_s_memtime(), ck_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
-  const int GM = e.gm;
-  const int per_group = GM * ntn;
-  auto tile_origin = [&](int t, int& m0, int& n0) {
-    const int group = t / per_group, first_m = group * GM;
-    const int gsz = min(ntm - first_m, GM);
-    m0 = (first_m + (t % per_group) % gsz) * 256;
-    n0 = ((t % per_group) / gsz) * 256;
-  };
-  auto fresh_lane = [&]() { int l = lane; asm volatile("" : "+v"(l)); return l; };
-  const size_t rowbytes = (size_t)K * sizeof(T);
-  // the tile being STAGED (the tile being computed until the switch in the second-to-last K-tile, the next one after it)
-  const char *a_base, *w_base;
-  uint32_t soff[4][2];
-  auto set_tile = [&](int m0, int n0) {
-    a_base = reinterpret_cast<const char*>(A) + (size_t)m0 * rowbytes;
-    w_base = reinterpret_cast<const char*>(W) + (size_t)n0 * rowbytes;
-    dma_offsets<COLS8>(fresh_lane(), wid, M - 1 - m0, (uint32_t)rowbytes, soff);
-  };
+  auto set_tile = [&](int m0, int n0) { src.template set<COLS8>(A, W, m0, n0, M, K, fresh_lane(lane), wid); };
+  auto stage = [&](int u, int kt) { src.stage(smem, wid, u, kt); };
   const int nkt = K / (128 / (int)sizeof(T));
-  auto unit_off = [](int u) { return (u == 0 ? 0 : u == 2 ? 1 : u == 3 ? 2 : 3) * P_UNIT; };
-  auto stage = [&](int u, int kt) {  // unit u of K-tile kt of the staged tile
-    char* dst = smem + (kt & 1) * P_BUF + unit_off(u) + wid * 2048;
-    const char* base = ((u == 0 || u == 2) ? w_base : a_base) + (size_t)kt * 128;
-    // (the `nt` policy on either operand's staging loads loses 3-10 %: profiles/r04_gemm_nt_stores_ab.txt)
-    __builtin_amdgcn_global_load_lds(base + soff[u][0], NOVA_LDS_PTR(dst), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds(base + soff[u][1], NOVA_LDS_PTR(dst + 1024), 16, 0, 0);
-  };
   const bool lds_bias = !TDMA && e.bias != nullptr;
-  auto stage_bias = [&](int n0) {  // the tile's 256 bias values -> LDS, by wave 0 (older than the units requested after it)
-    if (lds_bias && wid == 0)
-      __builtin_amdgcn_global_load_lds(reinterpret_cast<const char*>(e.bias + n0) + lane * 16, NOVA_LDS_PTR(smem + P_BIAS), 16, 0, 0);
+  auto stage_bias = [&](int n0) {
+    if (lds_bias) w.stage_bias(e.bias, n0, lane);
   };
 
-  int fr, fg;
-  f4v acc[4][8];  // [y fragment][x fragment]
-  PFrag<T> xf[4][2], yf0[2][2], yf1[2][2];
-  auto read_x = [&](const char* buf, int xi) {
-    const char* u = buf + xi * P_UNIT;
-#pragma unroll
-    for (int f = 0; f < 4; ++f)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) xf[f][kk] = punit_frag<T>(u, wr * 64 + f * 16 + fr, fg + 4 * kk);
-  };
-  auto read_y = [&](const char* buf, int yi, PFrag<T> (&yf)[2][2]) {
-    const char* u = buf + (2 + yi) * P_UNIT;
-#pragma unroll
-    for (int f = 0; f < 2; ++f)
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) yf[f][kk] = punit_frag<T>(u, wc * 32 + f * 16 + fr, fg + 4 * kk);
-  };
-  f4v bcol[2];
   // TDMA: the table rows of Y fragment y of tile rows m0 + wc*64 + 16 y + [0, 16) -> this wave's window (4 instructions of 4 rows)
   auto stage_table = [&](int m0, int y) {
     const int mb = min(__builtin_amdgcn_readfirstlane(m0 + wc * 64 + y * 16), M - 1);
     const int s0 = mb / e.L, l0 = mb - s0 * e.L;
     const int b0 = s0 % e.rope_batch, b1 = b0 + 1 == e.rope_batch ? 0 : b0 + 1;
-    const int ln = fresh_lane();
+    const int ln = fresh_lane(lane);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       int l = l0 + min(i * 4 + (ln >> 4), M - 1 - mb);  // rows past M reuse row M-1
@@ -833,102 +848,69 @@ __global__ __launch_bounds__(512, 2) void gemm256c_kernel(const T* __restrict__ 
       __builtin_amdgcn_global_load_lds(e.rope + ((size_t)sb * e.L + l) * 64 + (ln & 15) * 4, NOVA_LDS_PTR(smem + P_TAB + wid * 4096 + i * 1024), 16, 0, 0);
     }
   };
-  auto mma_quadrant = [&](int xi, int yi, PFrag<T> (&yf)[2][2], auto first_ktile) {
-    constexpr bool FIRST = decltype(first_ktile)::value;
-    f4v c0[4];
-    if constexpr (FIRST) {
-#pragma unroll
-      for (int x = 0; x < 4; ++x) c0[x] = f4v{bcol[xi][x], bcol[xi][x], bcol[xi][x], bcol[xi][x]};
-    }
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int f = 0; f < 2; ++f)
-#pragma unroll
-        for (int x = 0; x < 4; ++x)
-          acc[yi * 2 + f][xi * 4 + x] = pmma(yf[f][kk], xf[x][kk], (FIRST && kk == 0) ? c0[x] : acc[yi * 2 + f][xi * 4 + x]);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  auto read_bias = [&]() {
-    if constexpr (TDMA) return;  // in registers since the previous epilogue (or the kernel entry)
-#pragma unroll
-    for (int xi = 0; xi < 2; ++xi)
-      bcol[xi] = lds_bias ? *reinterpret_cast<const f4v*>(smem + P_BIAS + (wr * 128 + col_of<COLS8>(fr, xi)) * 4) : f4v{0.f, 0.f, 0.f, 0.f};
-  };
 
   int m0, n0, nm0 = 0, nn0 = 0;
   bool more = false;
-  // One K-tile = 4 phases (header comment). MODE 0: inside a tile (K-tiles 0 .. nkt-3): requests K-tiles kt+1, kt+2 of the same
-  // tile. MODE 1: the second-to-last K-tile: the staged tile switches to the next one between phases 1 and 2. MODE 2: the last
-  // K-tile: all four requests belong to the next tile. Without a next tile modes 1 / 2 request nothing and drain.
+  // One K-tile: each phase requests the unit 6 ahead in the FLAT sequence. MODE 0: inside a tile (K-tiles 0 .. nkt-3): requests
+  // K-tiles kt+1, kt+2 of the same tile. MODE 1: the second-to-last K-tile: the staged tile switches to the next one between phases
+  // 1 and 2. MODE 2: the last K-tile: all four requests belong to the next tile. Without a next tile modes 1 / 2 request nothing
+  // and drain.
   auto ktile = [&](int kt, auto first_ktile, auto mode_tag) {
     constexpr int MODE = decltype(mode_tag)::value;
-    const char* buf = smem + (kt & 1) * P_BUF;
-    read_x(buf, 0);
-    read_y(buf, 0, yf0);
-    if (MODE == 0 || MODE == 1) stage(2, kt + 1);
-    else if (more) stage(2, 0);
-    NOVA_BARRIER();
-    mma_quadrant(0, 0, yf0, first_ktile);
-    NOVA_BARRIER();
-    read_y(buf, 1, yf1);
-    if (MODE == 0 || MODE == 1) stage(3, kt + 1);
-    else if (more) stage(3, 0);
-    NOVA_BARRIER();
-    mma_quadrant(0, 1, yf1, first_ktile);
-    NOVA_BARRIER();
-    read_x(buf, 1);
-    if (MODE == 0) {
-      stage(0, kt + 2);
-    } else if (MODE == 1) {
-      if (more) {
-        set_tile(nm0, nn0);  // from here on the next tile is the staged one
-        stage_bias(nn0);
-        stage(0, 0);
-      }
-    } else if (more) {
-      stage(0, 1);
-    }
-    NOVA_BARRIER();
-    mma_quadrant(1, 1, yf1, first_ktile);
-    NOVA_BARRIER();
-    if (MODE == 0) {
-      stage(1, kt + 2);
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    } else if (MODE == 1) {
-      if (more) {
-        stage(1, 0);
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // the last K-tile of this tile has landed (and, wave 0, the next bias)
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-    } else if (more) {
-      stage(1, 1);
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // K-tile 0 of the next tile has landed
-    }
-    if constexpr (TDMA && MODE == 2) {
-      if (n0 < e.rope_cols) stage_table(m0, 0);  // behind the wait: the first fragment's table rows arrive under this tile's last MFMAs
-    }
-    NOVA_BARRIER();
-    mma_quadrant(1, 0, yf0, first_ktile);
-    NOVA_BARRIER();
+    w.template ktile<decltype(first_ktile)::value>(
+        kt,
+        [&] {
+          if (MODE == 0 || MODE == 1) stage(2, kt + 1);
+          else if (more) stage(2, 0);
+        },
+        [&] {
+          if (MODE == 0 || MODE == 1) stage(3, kt + 1);
+          else if (more) stage(3, 0);
+        },
+        [&] {
+          if (MODE == 0) {
+            stage(0, kt + 2);
+          } else if (MODE == 1) {
+            if (more) {
+              set_tile(nm0, nn0);  // from here on the next tile is the staged one
+              stage_bias(nn0);
+              stage(0, 0);
+            }
+          } else if (more) {
+            stage(0, 1);
+          }
+        },
+        [&] {
+          if (MODE == 0) {
+            stage(1, kt + 2);
+            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+          } else if (MODE == 1) {
+            if (more) {
+              stage(1, 0);
+              asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // the last K-tile of this tile has landed (and, wave 0, the next bias)
+            } else {
+              asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+          } else if (more) {
+            stage(1, 1);
+            asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // K-tile 0 of the next tile has landed
+          }
+          if constexpr (TDMA && MODE == 2) {
+            if (n0 < e.rope_cols) stage_table(m0, 0);  // behind the wait: the first fragment's table rows arrive under this tile's last MFMAs
+          }
+        });
   };
 
-  if (e.stagger > 0) {
-    const long long until = clock64() + (long long)e.stagger * (int)blockIdx.x / (int)gridDim.x;
-    while (clock64() < until) __builtin_amdgcn_s_sleep(8);
-  }
-  int it = slot;
-  auto tile_at = [&](int i) { return cbase + (e.rev ? csize - 1 - i : i); };
-  tile_origin(tile_at(it), m0, n0);
+  start_stagger(e.stagger);
+  int it = walk.first();
+  walk.origin(it, m0, n0);
   set_tile(m0, n0);
   auto load_bias_regs = [&](int n0) {  // TDMA: the lane's 8 bias values by ordinary loads, waited for on the spot (nothing else in flight)
-    const int f = fresh_lane() & 15;
+    const int f = fresh_lane(lane) & 15;
 #pragma unroll
     for (int xi = 0; xi < 2; ++xi)
-      bcol[xi] = e.bias ? *reinterpret_cast<const f4v*>(e.bias + n0 + wr * 128 + col_of<COLS8>(f, xi)) : f4v{0.f, 0.f, 0.f, 0.f};
-    asm volatile("" : "+v"(bcol[0]), "+v"(bcol[1]));
+      w.bcol[xi] = e.bias ? *reinterpret_cast<const f4v*>(e.bias + n0 + wr * 128 + col_of<COLS8>(f, xi)) : f4v{0.f, 0.f, 0.f, 0.f};
+    asm volatile("" : "+v"(w.bcol[0]), "+v"(w.bcol[1]));
   };
   if constexpr (TDMA) load_bias_regs(n0);
   stage_bias(n0);
@@ -938,12 +920,12 @@ __global__ __launch_bounds__(512, 2) void gemm256c_kernel(const T* __restrict__ 
   NOVA_BARRIER();
   if (wr == 1) NOVA_BARRIER();  // group 1 runs one barrier behind group 0 inside the K loop
   for (;;) {
-    { const int l = fresh_lane(); fr = l & 15; fg = l >> 4; }
+    w.set_lane(fresh_lane(lane));
     NOVA_STAMP(0);
-    const int nxt = it + nslot;
-    more = nxt < csize;
-    if (more) tile_origin(tile_at(nxt), nm0, nn0);
-    read_bias();
+    const int nxt = it + walk.nslot;
+    more = walk.has(nxt);
+    if (more) walk.origin(nxt, nm0, nn0);
+    if constexpr (!TDMA) w.template read_bias<COLS8>(lds_bias);  // (TDMA: in registers since the previous epilogue, or the kernel entry)
     NOVA_STAMP(1);
     ktile(0, std::true_type{}, std::integral_constant<int, 0>{});
     NOVA_STAMP(2);
@@ -962,50 +944,33 @@ __global__ __launch_bounds__(512, 2) void gemm256c_kernel(const T* __restrict__ 
     // ---- epilogue of tile (m0, n0): no LDS traffic, no DMA issued beside it
     int cm0 = m0, cn0 = n0;
     asm volatile("" : "+s"(cm0), "+s"(cn0));
-    { const int l = fresh_lane(); fr = l & 15; fg = l >> 4; }
-    const bool rot = EPI == E_ROPE && cn0 < e.rope_cols;
+    w.set_lane(fresh_lane(lane));
+    const int fr = w.fr, fg = w.fg;
+    auto& acc = w.acc;
+    const bool rot = EPI == EPI_ROPE && cn0 < e.rope_cols;
     const int nw = cn0 + wr * 128;  // the wave's first column; the lane's 4 columns of half xi start at nw + col_of(fr, xi)
     f4v cs[4][4];  // RoPE table rows of the lane's 16 output rows: (cos0, sin0, cos1, sin1) of the pairs in its 4 columns
     const bool same_cols = 64 % e.hd == 0;  // both 64-column halves of the wave see the same table columns (head_dim 64)
-    auto load_cs = [&](int xi) {
-      const int tcol = (nw + col_of<COLS8>(fr, xi)) % e.hd;
-#pragma unroll
-      for (int y = 0; y < 4; ++y) {
-        const int mb = min(__builtin_amdgcn_readfirstlane(cm0 + wc * 64 + y * 16), M - 1);
-        const int s0 = mb / e.L, l0 = mb - s0 * e.L;
-        const int b0 = s0 % e.rope_batch, b1 = b0 + 1 == e.rope_batch ? 0 : b0 + 1;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          int l = l0 + min(fg * 4 + r, M - 1 - mb);  // rows past M reuse row M-1 (never stored differently)
-          int sb = b0;
-          if (l >= e.L) { l -= e.L; sb = b1; }  // a 16-row block crosses at most one sequence boundary (L >= 16)
-          cs[y][r] = *reinterpret_cast<const f4v*>(e.rope + ((size_t)sb * e.L + l) * e.hd + tcol);
-        }
-      }
-    };
     // Output addressing: a wave-uniform 64-bit tile base + a 32-bit lane offset per row (rows past M are copies of row M-1 and store
     // the identical bytes there again, so every tile issues the same number of stores)
     OT* const ctile = C + (size_t)cm0 * N + nw;
     const int rlim = M - 1 - cm0;
     auto row_off = [&](int y, int r) { return (uint32_t)min(wc * 64 + y * 16 + fg * 4 + r, rlim) * (uint32_t)N; };
-    // 4 / 8 consecutive columns of output row (y, r): component r of 4 / 8 accumulators. The packing instruction takes any two
-    // registers, so nothing has to be moved together first.
     auto put4 = [&](int y, int r, int xi, f4v v) { store4<OT>(ctile + row_off(y, r) + col_of<false>(fr, xi), v); };
-    auto value4 = [&](int y, int r, int xi) { return f4v{acc[y][xi * 4][r], acc[y][xi * 4 + 1][r], acc[y][xi * 4 + 2][r], acc[y][xi * 4 + 3][r]}; };
     auto put8 = [&](int y, int r, f4v lo, f4v hi) { store8<OT>(ctile + row_off(y, r) + fr * 8, lo, hi); };
     // The elementwise epilogues run IN PLACE on the accumulators, one register quad (4 rows of one column) at a time: the packed
     // f32 forms (v_pk_mul / v_pk_fma, gelu_erf_fast4) take aligned register pairs, and applied to the per-row gathers of the
     // stores below they cost one v_mov per operand pair on top (194 moves in 1096 vector instructions of the fc1 epilogue).
     // (activations: applied row block by row block beside the stores, see act_rows below)
-    constexpr bool ACT_ROWS = NOVA_GEMM_ACT_ROWS && (EPI == E_GELU || EPI == E_SILU) && COLS8 && !TDMA;
-    if constexpr ((EPI == E_GELU || EPI == E_SILU) && !ACT_ROWS) {
+    constexpr bool ACT_ROWS = NOVA_GEMM_ACT_ROWS && (EPI == EPI_GELU || EPI == EPI_SILU) && COLS8 && !TDMA;
+    if constexpr ((EPI == EPI_GELU || EPI == EPI_SILU) && !ACT_ROWS) {
 #pragma unroll
       for (int y = 0; y < 4; ++y)
 #pragma unroll
         for (int x = 0; x < 8; ++x) acc[y][x] = epi_apply<OT, EPI, false>(acc[y][x], acc[y][x], 1.0f);
     }
-    const bool qs = EPI == E_ROPE && cn0 < e.q_cols;  // a q tile: results times the softmax scale (after the rotation)
-    if (EPI == E_ROPE && qs && !rot) {  // (not a combination the model produces: q columns are rotated)
+    const bool qs = EPI == EPI_ROPE && cn0 < e.q_cols;  // a q tile: results times the softmax scale (after the rotation)
+    if (EPI == EPI_ROPE && qs && !rot) {  // (not a combination the model produces: q columns are rotated)
 #pragma unroll
       for (int y = 0; y < 4; ++y)
 #pragma unroll
@@ -1021,7 +986,7 @@ __global__ __launch_bounds__(512, 2) void gemm256c_kernel(const T* __restrict__ 
 #pragma unroll
       for (int y = 0; y < 4; ++y)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) put4(y, r, xi, rope_rotate4(value4(y, r, xi), cs[y][r]) * qmul);
+        for (int r = 0; r < 4; ++r) put4(y, r, xi, rope_rotate4(w.value4(y, r, xi), cs[y][r]) * qmul);
     };
     auto plain_rows = [&]() {  // no rotation: the accumulators as they stand
 #pragma unroll
@@ -1029,10 +994,10 @@ __global__ __launch_bounds__(512, 2) void gemm256c_kernel(const T* __restrict__ 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           if constexpr (COLS8) {
-            put8(y, r, value4(y, r, 0), value4(y, r, 1));
+            put8(y, r, w.value4(y, r, 0), w.value4(y, r, 1));
           } else {
-            put4(y, r, 0, value4(y, r, 0));
-            put4(y, r, 1, value4(y, r, 1));
+            put4(y, r, 0, w.value4(y, r, 0));
+            put4(y, r, 1, w.value4(y, r, 1));
           }
         }
     };
@@ -1059,7 +1024,7 @@ __global__ __launch_bounds__(512, 2) void gemm256c_kernel(const T* __restrict__ 
             __builtin_amdgcn_sched_barrier(0);
             if (y < 3) stage_table(cm0, y + 1);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) put8(y, r, rotated(value4(y, r, 0), tlo[r], scaled), rotated(value4(y, r, 1), thi[r], scaled));
+            for (int r = 0; r < 4; ++r) put8(y, r, rotated(w.value4(y, r, 0), tlo[r], scaled), rotated(w.value4(y, r, 1), thi[r], scaled));
           }
         };
         if (qs) passes(std::true_type{});
@@ -1075,15 +1040,15 @@ __global__ __launch_bounds__(512, 2) void gemm256c_kernel(const T* __restrict__ 
 #pragma unroll
         for (int x = 0; x < 8; ++x) acc[y][x] = epi_apply<OT, EPI, false>(acc[y][x], acc[y][x], 1.0f);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) put8(y, r, value4(y, r, 0), value4(y, r, 1));
+        for (int r = 0; r < 4; ++r) put8(y, r, w.value4(y, r, 0), w.value4(y, r, 1));
         __builtin_amdgcn_sched_barrier(0);
       }
     } else if constexpr (COLS8) {
       plain_rows();
     } else if (rot) {
-      load_cs(0);  // (the compiler waits for everything in flight at their first use: the two units of the next tile's K-tile 1)
+      load_cs(e, M, cm0 + wc * 64, fg, nw + col_of<COLS8>(fr, 0), cs);  // (the compiler waits for everything in flight at their first use: the two units of the next tile's K-tile 1)
       finish_half(0);
-      if (!same_cols) load_cs(1);
+      if (!same_cols) load_cs(e, M, cm0 + wc * 64, fg, nw + col_of<COLS8>(fr, 1), cs);
       finish_half(1);
     } else {
       plain_rows();
@@ -1141,22 +1106,13 @@ constexpr int g_var256 = 20;     // the persistent form
 #endif
 
 template <typename T, int VAR>
-static int launch256v(const void* A, const void* W, void* C, int M, int N, int K, int epi, const GemmEpi256& e,
-                     hipStream_t st) {
+static int launch256v(const T* a, const T* w, T* c, int M, int N, int K, int epi, const GemmEpi256& e, hipStream_t st) {
   const int ntm = (M + 255) / 256, ntn = N / 256;
-  dim3 grid(ntm * ntn), block(512);
   ProfScope prof(prof_gemm_slot(epi, N, K), 2.0 * M * N * K, st);
-  const T* a = static_cast<const T*>(A);
-  const T* w = static_cast<const T*>(W);
-  T* c = static_cast<T*>(C);
-  switch (epi) {
-    case E_NONE: hipLaunchKernelGGL((gemm256_kernel<T, E_NONE, VAR>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    case E_GELU: hipLaunchKernelGGL((gemm256_kernel<T, E_GELU, VAR>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    case E_SILU: hipLaunchKernelGGL((gemm256_kernel<T, E_SILU, VAR>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    case E_ROPE: hipLaunchKernelGGL((gemm256_kernel<T, E_ROPE, VAR>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    default: return set_error(NOVA_ERR_ARG, "gemm256: unknown epilogue %d", epi);
-  }
-  return check_launch("gemm256");
+  const int rc = dispatch_epi(epi, [&](auto tag) {
+    hipLaunchKernelGGL((gemm256_kernel<T, decltype(tag)::value, VAR>), dim3(ntm * ntn), dim3(512), 0, st, a, w, c, M, N, K, ntm, ntn, e);
+  });
+  return rc ? rc : check_launch("gemm256");
 }
 
 #ifdef NOVA_EXPERIMENTS
@@ -1179,79 +1135,58 @@ static int cu_slots() {  // persistent grid: one workgroup per CU, a multiple of
 int gemm256_cu_count() { return cu_slots(); }  // the persistent grid = CUs of the device (gemm.hip's kernel choice reads it)
 
 template <typename T>
-static int launch256p(const void* A, const void* W, void* C, int M, int N, int K, int epi, const GemmEpi256& e,
-                      hipStream_t st) {
+static int launch256p(const T* a, const T* w, typename OutOf<T>::type* c, int M, int N, int K, int epi, const GemmEpi256& e, hipStream_t st) {
   const int ntm = (M + 255) / 256, ntn = N / 256;
   dim3 grid(cu_slots()), block(512);
-  ProfScope prof(prof_gemm_slot(epi, N, K), 2.0 * M * N * K, st);
-  const T* a = static_cast<const T*>(A);
-  const T* w = static_cast<const T*>(W);
-  T* c = static_cast<T*>(C);
-  switch (epi) {
-    case E_NONE: hipLaunchKernelGGL((gemm256p_kernel<T, E_NONE>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    case E_GELU: hipLaunchKernelGGL((gemm256p_kernel<T, E_GELU>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    case E_SILU: hipLaunchKernelGGL((gemm256p_kernel<T, E_SILU>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    case E_ROPE: hipLaunchKernelGGL((gemm256p_kernel<T, E_ROPE>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    default: return set_error(NOVA_ERR_ARG, "gemm256: unknown epilogue %d", epi);
+  ProfScope prof(prof_gemm_slot(epi == EPI_GELU_Q8 ? EPI_GELU : epi, N, K), 2.0 * M * N * K, st);
+  if constexpr (sizeof(T) == 1) {  // the e4m3-output epilogue exists for fp8 operands only
+    if (epi == EPI_GELU_Q8) {
+      hipLaunchKernelGGL((gemm256p_kernel<T, EPI_GELU_Q8>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e);
+      return check_launch("gemm256p");
+    }
   }
-  return check_launch("gemm256p");
+  const int rc = dispatch_epi(epi, [&](auto tag) {
+    hipLaunchKernelGGL((gemm256p_kernel<T, decltype(tag)::value>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e);
+  });
+  return rc ? rc : check_launch("gemm256p");
 }
 
 // MX-fp8 operands (OCP e4m3 bytes, K % 128 == 0), bf16 result; persistent kernel only. Internal entry for capi.hip.
-// epi E_ROPE: the fused-QKV epilogue (rotation of the first rope_cols columns with the [rope_batch, L, hd/2, 2] table,
+// epi EPI_ROPE: the fused-QKV epilogue (rotation of the first rope_cols columns with the [rope_batch, L, hd/2, 2] table,
 // q_scale on the first q_cols columns), applied after the dequantisation scales and the bias.
 int gemm256_fp8_launch(const void* A8, const float* sa, const void* W8, const float* sw, const float* bias, void* C, int M,
                        int N, int K, int epi, hipStream_t st, const float* rope, int L, int rope_batch, int hd, int rope_cols,
                        float q_scale, int q_cols, int sa_scalar, const float* q8_scale, unsigned* q8_amax) {
   if (M <= 0) return 0;
   if (N % 256 != 0 || K % 128 != 0 || K <= 0) return set_error(NOVA_ERR_SHAPE, "gemm_fp8: need N %% 256 == 0 and K %% 128 == 0 (got N=%d K=%d)", N, K);
-  if (epi == E_ROPE && (rope_cols % 256 || q_cols % 256 || (rope && (L < 16 || rope_batch <= 0 || hd <= 0))))
+  if (epi == EPI_ROPE && (rope_cols % 256 || q_cols % 256 || (rope && (L < 16 || rope_batch <= 0 || hd <= 0))))
     return set_error(NOVA_ERR_SHAPE, "gemm_fp8: RoPE epilogue needs rope_cols, q_cols %% 256 == 0 and L >= 16");
-  GemmEpi256 e{bias, rope, rope ? L : 1, rope ? rope_batch : 1, rope ? hd : 2, rope ? rope_cols : 0, q_scale, q_cols, g_gm256,
+  GemmEpi256 e{{bias, rope, rope ? L : 1, rope ? rope_batch : 1, rope ? hd : 2, rope ? rope_cols : 0, q_scale, q_cols}, g_gm256,
                walk_is_reverse() ? 1 : 0, sa, sw, 0};
   e.sa_scalar = sa_scalar;
   e.q8_scale = q8_scale;
   e.q8_amax = q8_amax;
-  if (epi == E_GELU_Q8 && (!q8_scale || !q8_amax)) return set_error(NOVA_ERR_ARG, "gemm_fp8: the e4m3-output epilogue needs a scale and an amax word");
-  const int ntm = (M + 255) / 256, ntn = N / 256;
-  dim3 grid(cu_slots()), block(512);
-  ProfScope prof(prof_gemm_slot(epi == E_GELU_Q8 ? E_GELU : epi, N, K), 2.0 * M * N * K, st);
-  const fp8_t* a = static_cast<const fp8_t*>(A8);
-  const fp8_t* w = static_cast<const fp8_t*>(W8);
-  bf16_t* c = static_cast<bf16_t*>(C);
-  switch (epi) {
-    case E_NONE: hipLaunchKernelGGL((gemm256p_kernel<fp8_t, E_NONE>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    case E_GELU: hipLaunchKernelGGL((gemm256p_kernel<fp8_t, E_GELU>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    case E_SILU: hipLaunchKernelGGL((gemm256p_kernel<fp8_t, E_SILU>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    case E_ROPE: hipLaunchKernelGGL((gemm256p_kernel<fp8_t, E_ROPE>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    case E_GELU_Q8: hipLaunchKernelGGL((gemm256p_kernel<fp8_t, E_GELU_Q8>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    default: return set_error(NOVA_ERR_ARG, "gemm_fp8: unknown epilogue %d", epi);
-  }
-  return check_launch("gemm256p fp8");
+  if (epi == EPI_GELU_Q8 && (!q8_scale || !q8_amax)) return set_error(NOVA_ERR_ARG, "gemm_fp8: the e4m3-output epilogue needs a scale and an amax word");
+  return launch256p<fp8_t>(static_cast<const fp8_t*>(A8), static_cast<const fp8_t*>(W8), static_cast<bf16_t*>(C), M, N, K, epi, e, st);
 }
 
 template <typename T>
-static int launch256c(const void* A, const void* W, void* C, int M, int N, int K, int epi, const GemmEpi256& e,
-                      hipStream_t st) {
+static int launch256c(const T* a, const T* w, T* c, int M, int N, int K, int epi, const GemmEpi256& e, hipStream_t st) {
   const int ntm = (M + 255) / 256, ntn = N / 256;
   dim3 grid(cu_slots()), block(512);
   ProfScope prof(prof_gemm_slot(epi, N, K), 2.0 * M * N * K, st);
-  const T* a = static_cast<const T*>(A);
-  const T* w = static_cast<const T*>(W);
-  T* c = static_cast<T*>(C);
-  switch (epi) {
-    case E_NONE: hipLaunchKernelGGL((gemm256c_kernel<T, E_NONE>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    case E_GELU: hipLaunchKernelGGL((gemm256c_kernel<T, E_GELU>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    case E_SILU: hipLaunchKernelGGL((gemm256c_kernel<T, E_SILU>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e); break;
-    case E_ROPE:
+  const int rc = dispatch_epi(epi, [&](auto tag) {
+    constexpr int EPI = decltype(tag)::value;
+    if constexpr (EPI == EPI_ROPE) {
       // head width 64 with a table: the table rows through LDS and 8 consecutive columns per lane; other head widths (96: d48w1536)
       // and the table-less q-scale-only use: table rows through registers, 4 consecutive columns per lane and column half
-      if (e.rope && e.hd == 64) hipLaunchKernelGGL((gemm256c_kernel<T, E_ROPE, true>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e);
-      else hipLaunchKernelGGL((gemm256c_kernel<T, E_ROPE, false>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e);
-      break;
-    default: return set_error(NOVA_ERR_ARG, "gemm256: unknown epilogue %d", epi);
-  }
-  return check_launch("gemm256c");
+      if (e.rope && e.hd == 64) hipLaunchKernelGGL((gemm256c_kernel<T, EPI_ROPE, true>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e);
+      else hipLaunchKernelGGL((gemm256c_kernel<T, EPI_ROPE, false>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e);
+    } else {
+      hipLaunchKernelGGL((gemm256c_kernel<T, EPI>), grid, block, 0, st, a, w, c, M, N, K, ntm, ntn, e);
+    }
+  });
+  return rc ? rc : check_launch("gemm256c");
 }
 
 // form: 0 = the shipped choice (continuous form where its preconditions hold, else the prologue form), 1 = one tile per
@@ -1259,30 +1194,32 @@ static int launch256c(const void* A, const void* W, void* C, int M, int N, int K
 template <typename T>
 static int launch256(const void* A, const void* W, void* C, int M, int N, int K, int epi, const GemmEpi256& e,
                      hipStream_t st, int form) {
+  const T* a = static_cast<const T*>(A);
+  const T* w = static_cast<const T*>(W);
+  T* c = static_cast<T*>(C);
   // (the persistent RoPE epilogues step through a 16-row block assuming it crosses at most one sequence boundary)
-  if (form != 1 && g_var256 == 20 && !(epi == E_ROPE && e.rope && e.L < 16)) {
+  if (form != 1 && g_var256 == 20 && !(epi == EPI_ROPE && e.rope && e.L < 16)) {
     const int nkt = K / (128 / (int)sizeof(T));
-    if (form == 0 && nkt >= 4 && (nkt & 1) == 0) return launch256c<T>(A, W, C, M, N, K, epi, e, st);
-    return launch256p<T>(A, W, C, M, N, K, epi, e, st);
+    if (form == 0 && nkt >= 4 && (nkt & 1) == 0) return launch256c<T>(a, w, c, M, N, K, epi, e, st);
+    return launch256p<T>(a, w, c, M, N, K, epi, e, st);
   }
 #ifdef NOVA_EXPERIMENTS
   switch (g_var256) {
-    case 1: return launch256v<T, 1>(A, W, C, M, N, K, epi, e, st);
-    case 3: return launch256v<T, 3>(A, W, C, M, N, K, epi, e, st);
-    case 0: return launch256v<T, 0>(A, W, C, M, N, K, epi, e, st);
-    case 10: return launch256v<T, 10>(A, W, C, M, N, K, epi, e, st);
-    case 11: return launch256v<T, 11>(A, W, C, M, N, K, epi, e, st);
-    case 12: return launch256v<T, 12>(A, W, C, M, N, K, epi, e, st);
+    case 1: return launch256v<T, 1>(a, w, c, M, N, K, epi, e, st);
+    case 3: return launch256v<T, 3>(a, w, c, M, N, K, epi, e, st);
+    case 0: return launch256v<T, 0>(a, w, c, M, N, K, epi, e, st);
+    case 10: return launch256v<T, 10>(a, w, c, M, N, K, epi, e, st);
+    case 11: return launch256v<T, 11>(a, w, c, M, N, K, epi, e, st);
+    case 12: return launch256v<T, 12>(a, w, c, M, N, K, epi, e, st);
     default: break;
   }
 #endif
-  return launch256v<T, 2>(A, W, C, M, N, K, epi, e, st);
+  return launch256v<T, 2>(a, w, c, M, N, K, epi, e, st);
 }
 
 // Entry used by gemm.hip's dispatcher. Preconditions (checked by the caller): N % 256 == 0,
 // K % (128 / sizeof(T)) == 0, K > 0, M > 0.
-int gemm256_launch(const void* A, const void* W, void* C, int M, int N, int K, int epi, const float* bias,
-                   const float* rope, int L, int rope_batch, int hd, int rope_cols, float q_scale, int q_cols, int dtype,
+int gemm256_launch(const void* A, const void* W, void* C, int M, int N, int K, int epi, const GemmEpi& epi_args, int dtype,
                    hipStream_t st, int form) {
 #ifdef NOVA_EXPERIMENTS
   const int gm = g_gm256;
@@ -1291,7 +1228,7 @@ int gemm256_launch(const void* A, const void* W, void* C, int M, int N, int K, i
   // (the out-projection: 0.282 against 0.294 ms at 163840 x 1024 x 1024; K = 4096 loses 6 % with 16: profiles/r04_gemm_group_height_sweep.txt)
   const int gm = (N <= 1024 && K * (int)(dtype_is16(dtype) ? 2 : 4) <= 2048) ? 16 : g_gm256;
 #endif
-  GemmEpi256 e{bias, rope, L, rope_batch, hd, rope_cols, q_scale, q_cols, gm, walk_is_reverse() ? 1 : 0, nullptr, nullptr, g_stagger256};
+  GemmEpi256 e{epi_args, gm, walk_is_reverse() ? 1 : 0, nullptr, nullptr, g_stagger256};
   return dispatch_dtype(dtype, [&](auto tag) { return launch256<decltype(tag)>(A, W, C, M, N, K, epi, e, st, form); });
 }
 

@@ -1,6 +1,7 @@
 // Internal declarations shared by the kernel translation units and the C ABI (capi.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "../../include/nova_hip.h"
 
 #include "common.h"
@@ -39,7 +40,33 @@ struct ProfScope {
   hipStream_t st;
 };
 
-// ---- gemm.hip
+// ---- gemm.hip, gemm256.hip: the epilogue of out = epi(A W^T + bias), one vocabulary for every GEMM structure
+struct GemmEpi {
+  const float* bias;     // [N] or nullptr
+  const float* rope;     // [rope_batch, L, hd/2, 2] (cos, sin) or nullptr
+  int L;                 // tokens per sequence (rows m -> (s = m / L, l = m % L))
+  int rope_batch;        // table batch count; sequence s uses table s % rope_batch
+  int hd;                // head dim
+  int rope_cols;         // columns [0, rope_cols) are rotated (q and k thirds of the fused QKV)
+  float q_scale;         // columns [0, q_cols) are multiplied by this after rotation (softmax scale folded into q)
+  int q_cols;
+};
+// EPI_NONE .. EPI_SILU are the public activation codes (NOVA_ACT_*). EPI_GELU_Q8 (fp8 operands only, gemm256.hip): GELU, then the
+// result is written as OCP e4m3 bytes, value / *q8_scale saturated at +-448, instead of bf16 - the A operand of the next fp8 GEMM
+// without a quantisation pass ("delayed scaling": the caller derives the next call's scale from q8_amax).
+enum { EPI_NONE = 0, EPI_GELU = 1, EPI_SILU = 2, EPI_ROPE = 3, EPI_GELU_Q8 = 5 };
+constexpr int NOVA_EPI_GELU_Q8 = EPI_GELU_Q8;  // (the name capi.hip calls it by)
+// epilogue code -> compile-time tag, for the four epilogues every structure and storage type has: f(std::integral_constant<int, EPI_x>{})
+// launches; returns 0, or the error for any other code
+template <typename F> inline int dispatch_epi(int epi, F&& f) {
+  switch (epi) {
+    case EPI_NONE: f(std::integral_constant<int, EPI_NONE>{}); return 0;
+    case EPI_GELU: f(std::integral_constant<int, EPI_GELU>{}); return 0;
+    case EPI_SILU: f(std::integral_constant<int, EPI_SILU>{}); return 0;
+    case EPI_ROPE: f(std::integral_constant<int, EPI_ROPE>{}); return 0;
+    default: return set_error(NOVA_ERR_ARG, "gemm: unknown epilogue %d", epi);
+  }
+}
 int gemm_bias_act(const void* A, const void* W, const float* bias, void* out, int M, int N, int K, int act,
                   int dtype, hipStream_t st);
 int gemm_qkv_rope(const void* x, const void* Wqkv, const float* bias, const float* rope, void* qkv, int S, int L,
@@ -120,7 +147,6 @@ int gemm256_fp8_launch(const void* A8, const float* sa, const void* W8, const fl
                        int N, int K, int epi, hipStream_t st, const float* rope = nullptr, int L = 1, int rope_batch = 1,
                        int hd = 2, int rope_cols = 0, float q_scale = 1.0f, int q_cols = 0, int sa_scalar = 0,
                        const float* q8_scale = nullptr, unsigned* q8_amax = nullptr);
-constexpr int NOVA_EPI_GELU_Q8 = 5;  // gemm256.hip E_GELU_Q8: GELU + e4m3 output with a static scale (fp8 operands only)
 int silu_add_rows(const void* a, const void* rowvec, void* out, long rows, int D, int dtype, hipStream_t st);
 int silu_add_steps(const void* a, const void* vecs, void* out, long rows, int nvec, int D, int dtype, hipStream_t st);
 int timestep_freq(const float* t, const float* freq, void* out, int n, int freq_dim, int dtype, hipStream_t st);

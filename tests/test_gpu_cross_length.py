@@ -129,13 +129,33 @@ def test_qkv_rope_cols(hip, dtype, D, heads, use):
 
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("D,heads", [(256, 4), (768, 8)])
-def test_qkv_rope_cols_large_m_tiles_bitwise(hip, force_tile, dtype, D, heads):
-    """M = 5 * 821 = 4105 rows (where the 256 x 256 structure takes over), head_dim 64 and 96: the 128 and the 256 tile
-    give the same bits, and those are right."""
+@pytest.mark.parametrize("form", [256, 257, 258])
+def test_qkv_rope_cols_large_m_tiles_bitwise(hip, force_tile, dtype, D, heads, form):
+    """M = 5 * 821 = 4105 rows (where the 256 x 256 structure takes over), head_dim 64 and 96: the 128 tile and every form
+    of the 256 tile (256 the shipped choice, 257 one tile per workgroup, 258 the persistent prologue form) give the same
+    bits, and those are right. Head width 96 is where the persistent forms load a second set of table rows."""
     hd = D // heads
     S, L, N = 5, 821, 2 * D
     x, w = randn(S * L, D, seed=61).to(dtype), randn(N, D, seed=62, scale=D ** -0.5).to(dtype)
     b, rope = randn(N, seed=63), C.make_rope(2, L, hd, torch.Generator().manual_seed(64))
+    xd, wd, bd, rd = x.to(DEV), w.to(DEV), b.to(DEV), rope.to(DEV)
+    force_tile(128)
+    o128 = hip.qkv_rope_cols(xd, wd, bd, rd, L, hd, D)
+    force_tile(form)
+    o256 = hip.qkv_rope_cols(xd, wd, bd, rd, L, hd, D)
+    assert same_bits(o128, o256)
+    check_rope_cols(o256, rope_cols_ref(x, w, b, rope, S, L, heads, D), D, dtype)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_qkv_rope_cols_short_sequence_256_tile_bitwise(hip, force_tile, dtype):
+    """A rotated launch with L = 5 < 16 sent to the 256 tile takes its one-tile-per-workgroup kernel (the persistent
+    epilogues step through 16-row blocks that cross at most one sequence boundary). M = 61 * 5 = 305: two row tiles, the
+    second ragged, M no multiple of L * rope_batch. Same bits as the 128 tile, and those are right."""
+    S, L, D, heads = 61, 5, 256, 4
+    hd, N = D // heads, 2 * D
+    x, w = randn(S * L, D, seed=65).to(dtype), randn(N, D, seed=66, scale=D ** -0.5).to(dtype)
+    b, rope = randn(N, seed=67), C.make_rope(2, L, hd, torch.Generator().manual_seed(68))
     xd, wd, bd, rd = x.to(DEV), w.to(DEV), b.to(DEV), rope.to(DEV)
     force_tile(128)
     o128 = hip.qkv_rope_cols(xd, wd, bd, rd, L, hd, D)

@@ -78,3 +78,16 @@ for tag, N, K, act in (("out-projection 163840 x 1024 x 1024", 1024, 1024, 0), (
         ab("LayerNorm/residual pass + QKV + RoPE", norm_then_qkv)
         ab("LayerNorm/residual pass alone", lambda lib: lambda: lib.nova_row_norm(o_.data_ptr(), out_.data_ptr(), gam.data_ptr(), bet.data_ptr(), None, 0, -1, -1, -1, res_.data_ptr(), None, S * L, N, 1e-5, 1, st))
     del a_, w_, o_
+
+# the two fp8 launches the encoder's fp8 configuration adds (the persistent prologue form): fc1 + GELU and the fused QKV + RoPE
+x8, xs = torch.empty(S * L, D, dtype=torch.uint8, device="cuda"), torch.empty(S * L, device="cuda")
+libs[0].nova_quantize_rows_fp8(x.data_ptr(), x8.data_ptr(), xs.data_ptr(), S * L, D, st)
+for tag, N, call in (("fp8 fc1 + GELU 163840 x 4096 x 1024", 4 * D, "gemm"), ("fp8 QKV + RoPE 163840 x 3072 x 1024", 3 * D, "qkv")):
+    w_, w8, ws = rnd(N, D, scale=D ** -0.5), torch.empty(N, D, dtype=torch.uint8, device="cuda"), torch.empty(N, device="cuda")
+    libs[0].nova_quantize_rows_fp8(w_.data_ptr(), w8.data_ptr(), ws.data_ptr(), N, D, st)
+    b_, o_ = torch.randn(N, device="cuda"), torch.empty(S * L, N, dtype=dt, device="cuda")
+    if call == "gemm":
+        ab(tag, lambda lib: lambda: lib.nova_gemm_fp8_bias_act(x8.data_ptr(), xs.data_ptr(), w8.data_ptr(), ws.data_ptr(), b_.data_ptr(), o_.data_ptr(), S * L, N, D, 1, st), 2.0 * S * L * N * D)
+    else:
+        ab(tag, lambda lib: lambda: lib.nova_qkv_rope_fp8(x8.data_ptr(), xs.data_ptr(), w8.data_ptr(), ws.data_ptr(), b_.data_ptr(), rope.data_ptr(), o_.data_ptr(), S, L, D, heads, 2, 1.0, st), 2.0 * S * L * N * D)
+
