@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NOVA_HIP_VERSION 405 /* still 0.4.5 (tests/test_pointset_fps.py pins the number; a library without the new symbols fails to bind, loudly): nova_pointset_knn (exact k nearest neighbours of a cloud set); nova_pointset_assignment, nova_pointset_assignment_state_bytes, nova_pointset_assignment_rounds (optimal assignment of two clouds by a batched integer auction: the exact EMD on the GPU); 0.4.5: nova_pointset_farthest_point_sample (farthest point sampling of a cloud set, to bring sets to a common point count); 0.4.4: nova_pointset_occupancy_grid (occupancy grid of a cloud set for the JSD metric); 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
+#define NOVA_HIP_VERSION 405 /* still 0.4.5 (tests/test_pointset_fps.py pins the number; a library without the new symbols fails to bind, loudly): nova_pointset_nearest_match, nova_pointset_nearest_match_bwd (nearest match with indices and its backward, for the Chamfer-type training losses); nova_pointset_knn (exact k nearest neighbours of a cloud set); nova_pointset_assignment, nova_pointset_assignment_state_bytes, nova_pointset_assignment_rounds (optimal assignment of two clouds by a batched integer auction: the exact EMD on the GPU); 0.4.5: nova_pointset_farthest_point_sample (farthest point sampling of a cloud set, to bring sets to a common point count); 0.4.4: nova_pointset_occupancy_grid (occupancy grid of a cloud set for the JSD metric); 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
 
 typedef enum { NOVA_F32 = 0, NOVA_BF16 = 1, NOVA_F16 = 2 } nova_dtype;
 typedef enum { NOVA_ACT_NONE = 0, NOVA_ACT_GELU_ERF = 1, NOVA_ACT_SILU = 2 } nova_act;
@@ -416,6 +416,40 @@ int nova_pointset_knn(const float* x, const float* y, int* idx, float* d2, int S
 #define NOVA_INTERP_MAX_CHANNELS 8
 int nova_pointset_kernel_interpolate(const float* q, const float* p, const float* v, float* out,
                                      int S, int T, int N, int C, float scale, void* stream);
+
+/* Nearest match with indices, and its backward: the primitive under the Chamfer-type training losses of the reference,
+ * robust_chamfer_distance on distChamfer (train_newloss.py:316-349) and the edge-consistency term (train_newloss.py:449-457:
+ * torch.cdist(subset1, subset2).min(dim=1), mean), which in PyTorch keep a [B, N, M] cdist matrix alive for the backward.
+ * Neither pass stores an [N, M] array here. x [B, N, 3], y [B, M, 3] float32, finite.
+ * Point map p(v), the one of nova_pointset_nn_dist: c_k = min(max(v_k, clamp_lo), clamp_hi) per coordinate; unit_norm != 0:
+ *   n = sqrtf((fmaf(c1, c1, c0 * c0)) + c2 * c2), inv = 1 / max(n, 1e-8) (one IEEE division), p_k = c_k * inv; otherwise p = c.
+ * Every operation named is rounded once to float32; nothing else is fused.
+ * nova_pointset_nearest_match: for every x[b, i] the smallest key (sqdist3(p(x_i), p(y_j)), j) in lexicographic order over
+ *   j in 0 .. M-1, sqdist3 the expression of nova_pointset_knn; ties in distance go to the lowest j (the rule of
+ *   nova_pointset_knn). d[b, i] = sqrtf(that d2) (float32, bit for bit the output of nova_pointset_nn_dist) and idx[b, i] = j
+ *   (int32).
+ * nova_pointset_nearest_match_bwd: from g[b, i] = dL/dd[b, i] and the forward's idx, gx [B, N, 3] and gy [B, M, 3] (float32).
+ *   With a = idx[b, i], u = p(x_i) - p(y_a) per axis and dist = sqrtf(sqdist3(p(x_i), p(y_a))), all recomputed:
+ *     t_i = (g_i * u) / dist per axis, the product rounded, then one IEEE division;  t_i = 0 exactly when dist == 0
+ *   (the subgradient convention: coincident points give no NaN and no gradient). An idx outside 0 .. M-1 is never
+ *   dereferenced and has t_i = 0. The pull-back P_v(t) through p at a point v, with c, n, inv, p as above:
+ *     unit_norm, n >= 1e-8:  w_k = fmaf(-p_k, s, t_k) with s = fmaf(p2, t2, fmaf(p1, t1, p0 * t0));  r_k = w_k * inv
+ *                            ((I - p p^T) t / n)
+ *     unit_norm, n <  1e-8:  r_k = t_k * inv   (inv is 1e8: torch's gradient of c / clamp_min(|c|, 1e-8) below the floor)
+ *     otherwise:             r = t
+ *     then r_k = 0 for every coordinate with v_k outside [clamp_lo, clamp_hi], bounds inclusive (torch.clamp's backward).
+ *   gx[b, i] = P_{x_i}(t_i).  gy[b, j] = P_{y_j}(-S_j), S_j = the sum of t_i over the i with idx[b, i] == j, added one by one
+ *   IN INCREASING i starting from +0 (a y_j nobody matched gets P(-0)). gy is a gather, one thread per y_j walking all i:
+ *   no atomics, no sort, one order of summation.
+ * Consequences: d, idx, gx and gy of a cloud depend on (x[b], y[b], g[b], the clamp, unit_norm) alone: bitwise the same for
+ * every batch, launch split, position in the batch and run.
+ * No clamp: pass -inf and +inf. NOVA_ERR_SHAPE for M <= 0 (an empty target set) and for B > 65535; NOVA_ERR_ARG for a null
+ * pointer and for clamp_lo > clamp_hi (or either NaN). B <= 0 or N <= 0 is a no-op returning 0, as in nova_pointset_nn_dist
+ * (gy is then not written). Everything is checked before any device work. Added without a version bump. */
+int nova_pointset_nearest_match(const float* x, const float* y, float* d, int* idx, int B, int N, int M, float clamp_lo,
+                                float clamp_hi, int unit_norm, void* stream);
+int nova_pointset_nearest_match_bwd(const float* x, const float* y, const int* idx, const float* g, float* gx, float* gy, int B,
+                                    int N, int M, float clamp_lo, float clamp_hi, int unit_norm, void* stream);
 
 /* Optimal assignment between x [B, n, 3] and y [B, n, 3] (float32, finite), pair by pair: the permutation that minimises
  * the mean matched distance, i.e. the earth mover's distance that compute_emd_distance (test_optimize.py:385-415) and

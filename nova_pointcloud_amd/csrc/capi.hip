@@ -458,6 +458,20 @@ int nova_pointset_pairwise_dist(const float* x, const float* y, float* D, int B,
   return pointset_pairwise_dist(x, y, D, B, N, M, clamp_lo, clamp_hi, (hipStream_t)stream);
 }
 
+int nova_pointset_nearest_match(const float* x, const float* y, float* d, int* idx, int B, int N, int M, float clamp_lo,
+                                float clamp_hi, int unit_norm, void* stream) {
+  NOVA_REQUIRE(B <= 0 || N <= 0 || (x && y && d && idx),NOVA_ERR_ARG, "pointset_nearest_match: null pointer");
+  NOVA_REQUIRE(clamp_lo <= clamp_hi, NOVA_ERR_ARG, "pointset_nearest_match: empty clamp range");
+  return pointset_nearest_match(x, y, d, idx, B, N, M, clamp_lo, clamp_hi, unit_norm, (hipStream_t)stream);
+}
+
+int nova_pointset_nearest_match_bwd(const float* x, const float* y, const int* idx, const float* g, float* gx, float* gy, int B,
+                                    int N, int M, float clamp_lo, float clamp_hi, int unit_norm, void* stream) {
+  NOVA_REQUIRE(B <= 0 || N <= 0 || (x && y && idx && g && gx && gy), NOVA_ERR_ARG, "pointset_nearest_match_bwd: null pointer");
+  NOVA_REQUIRE(clamp_lo <= clamp_hi, NOVA_ERR_ARG, "pointset_nearest_match_bwd: empty clamp range");
+  return pointset_nearest_match_bwd(x, y, idx, g, gx, gy, B, N, M, clamp_lo, clamp_hi, unit_norm, (hipStream_t)stream);
+}
+
 int nova_pointset_chamfer_matrix(const float* x, const float* y, float* cd, int A, int B, int N, int M, int ldc, int symmetric,
                                  void* stream) {
   NOVA_REQUIRE(A <= 0 || B <= 0 || (x && y && cd), NOVA_ERR_ARG, "pointset_chamfer_matrix: null pointer");

@@ -171,6 +171,11 @@ int modulate_rows(const void* x, const void* mod, void* out, long rows, int D, i
 // ---- pointset.hip (Chamfer / EMD distance work)
 int pointset_nn_dist(const float* x, const float* y, float* d, int B, int N, int M, float lo, float hi, int unit, hipStream_t st);
 int pointset_pairwise_dist(const float* x, const float* y, float* D, int B, int N, int M, float lo, float hi, hipStream_t st);
+// ---- nearest_match.hip (nearest match with indices and its backward: the Chamfer-type training losses)
+int pointset_nearest_match(const float* x, const float* y, float* d, int* idx, int B, int N, int M, float lo, float hi, int unit,
+                           hipStream_t st);
+int pointset_nearest_match_bwd(const float* x, const float* y, const int* idx, const float* g, float* gx, float* gy, int B, int N, int M,
+                               float lo, float hi, int unit, hipStream_t st);
 // ---- chamfer.hip (all-pairs Chamfer matrix for MMD / COV / 1-NNA)
 int pointset_chamfer_matrix(const float* x, const float* y, float* cd, int A, int B, int N, int M, int ldc, int symmetric,
                             hipStream_t st);

@@ -15,18 +15,7 @@ namespace nova {
 
 constexpr int PS_TILE = 1024;  // y points staged per LDS tile (12 KiB)
 
-// unit != 0: points are scaled to unit norm after clamping (distChamfer, train_newloss.py:325-337: x / max(|x|, 1e-8))
-__device__ __forceinline__ void load_point(const float* p, float lo, float hi, int unit, float& a, float& b, float& c) {
-  a = clampf(p[0], lo, hi);
-  b = clampf(p[1], lo, hi);
-  c = clampf(p[2], lo, hi);
-  if (unit) {
-    const float inv = 1.0f / fmaxf(sqrtf(a * a + b * b + c * c), 1e-8f);
-    a *= inv;
-    b *= inv;
-    c *= inv;
-  }
-}
+// load_point (pointset_common.h) is the point map: clamp, and with unit != 0 the scaling to unit norm after it
 
 __global__ __launch_bounds__(256) void nn_dist_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                       float* __restrict__ d, int N, int M, float lo, float hi, int unit) {

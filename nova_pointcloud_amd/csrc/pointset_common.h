@@ -24,6 +24,33 @@ __device__ __forceinline__ float sqdist3(float px, float py, float pz, float qx,
   return __builtin_fmaf(e2, e2, __builtin_fmaf(e1, e1, __fmul_rn(e0, e0)));
 }
 
+// |c| of a clamped point, as the unit-norm point map takes it: a a and c c rounded to float32, b b fused onto a a, the two
+// halves added, the square root correctly rounded. Contraction is off for the operators written inside (__fmul_rn and
+// __fadd_rn are plain * and + compiled elsewhere, which the pragma does not reach), so the expression is these five
+// roundings in every kernel that inlines it.
+__device__ __forceinline__ float norm3(float a, float b, float c) {
+#pragma clang fp contract(off)
+  const float aa = a * a, cc = c * c;
+  const float ab = __builtin_fmaf(b, b, aa);
+  return sqrtf(ab + cc);
+}
+
+// The point map p of nn_dist, nearest_match and its backward: every coordinate clamped to [lo, hi]; unit != 0: then scaled
+// by inv = 1 / max(|c|, 1e-8) (distChamfer, train_newloss.py:325-337: x / max(|x|, 1e-8)). The three products are rounded
+// to float32 and never fused into a caller's subtraction.
+__device__ __forceinline__ void load_point(const float* p, float lo, float hi, int unit, float& a, float& b, float& c) {
+#pragma clang fp contract(off)
+  a = clampf(p[0], lo, hi);
+  b = clampf(p[1], lo, hi);
+  c = clampf(p[2], lo, hi);
+  if (unit) {
+    const float inv = 1.0f / fmaxf(norm3(a, b, c), 1e-8f);
+    a = a * inv;
+    b = b * inv;
+    c = c * inv;
+  }
+}
+
 // Workgroup sum in a fixed order: wave_sum's pairing inside each wave, then the WAVES waves in index order through one
 // LDS slot each. Every thread gets the sum. Earlier code may still be reading red, so a barrier comes first.
 template <int WAVES> __device__ __forceinline__ float block_sum_fixed(float v, float* red) {

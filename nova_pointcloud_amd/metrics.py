@@ -56,7 +56,7 @@ def _points(t, name):
     if t.requires_grad and torch.is_grad_enabled():
         # evaluation metrics: the HIP distance kernels have no backward, so a loss built on them would silently carry no gradient
         raise hip.NovaHipError(f"{name}: nova_pointcloud_amd.metrics is evaluation-only (no autograd through the HIP kernels); "
-                               "detach the points or compute a training loss in PyTorch")
+                               "detach the points, or build a training loss on nova_pointcloud_amd.losses")
     return t.detach().float().contiguous()
 
 
