@@ -17,20 +17,15 @@
 // f32 kernel (parity mode): same skeleton on v_mfma_f32_32x32x2_f32 (exact f32), 32-key tiles.
 // head_dim 64 (d48w768 / d48w1024) and 96 (d48w1536: the K/V tile is staged as a 64-wide image plus a 32-wide
 // image so every LDS-DMA piece stays row-aligned and both images keep conflict-free read patterns).
+#include "attn_tile.h"
 #include "common.h"
 #include "nova_internal.h"
 
 namespace nova {
 
-constexpr float NEG_INF = -__builtin_huge_valf();
-
 // ------------------------------------------------------------------------------------------
-// bf16, head_dim HD in {64, 96}
+// bf16, head_dim HD in {64, 96}: workgroup decode, K/V tile images (Layout32), staging and Q load from attn_tile.h
 // ------------------------------------------------------------------------------------------
-constexpr int A_KV = 64;                 // keys per tile
-constexpr int A_T64 = A_KV * 128;        // 64-wide image: 128-byte rows, 8 KiB
-constexpr int A_T32 = A_KV * 64;         // 32-wide image (HD = 96 only): 64-byte rows, 4 KiB
-
 // q arrives scaled by (softmax scale * log2 e) - folded into the fused QKV GEMM epilogue by the block composite, or
 // applied at load (c != 1) for generic callers - and the running max is carried as the C operand of the first
 // QK^T MFMA (a 16-register block holding -m), so the softmax needs no multiply-subtract per score: p = exp2(acc).
@@ -40,80 +35,25 @@ __global__ __launch_bounds__(256, HD == 64 ? 3 : 2) void attn_bf16(const E* __re
                                                                     const E* __restrict__ v, E* __restrict__ o,
                                                                     int Lq, int Lk, long q_rs, long kv_rs, long o_rs, float c,
                                                                     int heads, int nq, int rev, long kv_ss, float* __restrict__ lse) {
-  constexpr int NKS = HD / 16, NDV = HD / 32;
-  constexpr int BUF = 2 * A_T64 + (HD == 96 ? 2 * A_T32 : 0);  // [K64 | V64 | K32 | V32]
+  constexpr int NKS = HD / 16, NDV = HD / 32, BUF = AT_BUF<HD>;
+  using I = Image<Layout32>;
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform: LDS-DMA bases stay scalar
   const int r = lane & 31, hh = lane >> 5;
-  // XCD-aware order: all query tiles of one (sequence, head) are consecutive in the remapped list, so they
-  // run on one XCD and its K/V is served from that XCD's L2 after the first tile.
-  const int t = xcd_remap_dir(blockIdx.x, gridDim.x, rev != 0);
-  const int sh = t / nq, qt = t - sh * nq;
-  const int head = sh % heads, s = sh / heads;
-  const int q0 = qt * 128 + wid * 32;
-
-  const E* qb = q + (size_t)s * Lq * q_rs + head * HD;
-  const E* kb_ = k + (size_t)s * kv_ss + head * HD;
-  const E* vb_ = v + (size_t)s * kv_ss + head * HD;
+  const AttnWg wg(blockIdx.x, gridDim.x, rev, nq, heads, 128);
+  const int q0 = wg.row0 + wid * 32;
+  const E* kb_ = wg.seq(k, kv_ss, HD);
+  const E* vb_ = wg.seq(v, kv_ss, HD);
 
   // Q fragments: B operand of S^T = K Q^T; lane (r, hh) holds Q[q0 + r][16 ks + 8 hh + 0..7]
   u4v qf[NKS];
-  {
-    const int qrow = min(q0 + r, Lq - 1);
-    const E* qp = qb + (size_t)qrow * q_rs + 8 * hh;
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) qf[ks] = *reinterpret_cast<const u4v*>(qp + 16 * ks);
-    if (c != 1.0f) {  // q not pre-scaled by the producer (generic nova_attn_fwd callers)
-#pragma unroll
-      for (int ks = 0; ks < NKS; ++ks)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const f2v t = Half16<E>::unpack(qf[ks][j]);
-          qf[ks][j] = Half16<E>::pack(t[0] * c, t[1] * c);
-        }
-    }
-  }
+  load_q<E, 16>(wg.seq(q, (long)Lq * q_rs, HD) + (size_t)min(q0 + r, Lq - 1) * q_rs + 8 * hh, c, qf);
 
-  // staging: wave w moves LDS-DMA pieces 2w, 2w+1 (8 rows x 128 B) of the 64-wide K and V images and, for
-  // HD = 96, piece w (16 rows x 64 B) of the 32-wide images. Per-lane byte offsets inside a tile are loop
-  // invariant (32-bit); the tile base advances as a wave-uniform scalar, so a full tile costs no vector address
-  // arithmetic. Only the ragged last tile recomputes clamped rows.
-  const uint32_t rowB = (uint32_t)kv_rs * 2u;
-  const int srow0 = (wid * 2) * 8 + (lane >> 3), srow1 = srow0 + 8, scp = lane & 7;
-  const int srow32 = wid * 16 + (lane >> 2), scp32 = lane & 3;
-  const uint32_t ck0 = (uint32_t)((scp ^ ((srow0 >> 1) & 7)) << 4), ck1 = (uint32_t)((scp ^ ((srow1 >> 1) & 7)) << 4);
-  const uint32_t cv0 = (uint32_t)((scp ^ (((srow0 >> 1) & 1) << 2)) << 4), cv1 = (uint32_t)((scp ^ (((srow1 >> 1) & 1) << 2)) << 4);
-  const uint32_t ck32 = 128u + (uint32_t)((scp32 ^ ((srow32 >> 2) & 3)) << 4), cv32 = 128u + (uint32_t)(scp32 << 4);
-  const uint32_t ko0 = srow0 * rowB + ck0, ko1 = srow1 * rowB + ck1, vo0 = srow0 * rowB + cv0, vo1 = srow1 * rowB + cv1;
-  const uint32_t ko32 = srow32 * rowB + ck32, vo32 = srow32 * rowB + cv32;
+  const KvStage<Layout32, HD> kv(wid, lane, kv_rs);
   auto stage = [&](int buf, int kt) {
     char* lk = smem + buf * BUF;
-    char* lv = lk + A_T64;
-    const char* kbase = reinterpret_cast<const char*>(kb_) + (size_t)kt * A_KV * rowB;  // wave-uniform
-    const char* vbase = reinterpret_cast<const char*>(vb_) + (size_t)kt * A_KV * rowB;
-    const int lim = Lk - 1 - kt * A_KV;  // last valid row of this tile
-    if (lim >= A_KV - 1) {
-      glds16(kbase, ko0, lk + wid * 2048);
-      glds16(vbase, vo0, lv + wid * 2048);
-      glds16(kbase, ko1, lk + wid * 2048 + 1024);
-      glds16(vbase, vo1, lv + wid * 2048 + 1024);
-      if constexpr (HD == 96) {
-        glds16(kbase, ko32, lk + 2 * A_T64 + wid * 1024);
-        glds16(vbase, vo32, lk + 2 * A_T64 + A_T32 + wid * 1024);
-      }
-    } else {  // ragged tile: rows past Lk re-read the last valid row (their scores are masked to -inf)
-      const uint32_t r0 = (uint32_t)min(srow0, lim) * rowB, r1 = (uint32_t)min(srow1, lim) * rowB;
-      glds16(kbase, r0 + ck0, lk + wid * 2048);
-      glds16(vbase, r0 + cv0, lv + wid * 2048);
-      glds16(kbase, r1 + ck1, lk + wid * 2048 + 1024);
-      glds16(vbase, r1 + cv1, lv + wid * 2048 + 1024);
-      if constexpr (HD == 96) {
-        const uint32_t r32 = (uint32_t)min(srow32, lim) * rowB;
-        glds16(kbase, r32 + ck32, lk + 2 * A_T64 + wid * 1024);
-        glds16(vbase, r32 + cv32, lk + 2 * A_T64 + A_T32 + wid * 1024);
-      }
-    }
+    kv.stage(kv.tile(kb_, kt), kv.tile(vb_, kt), kv.last_row(Lk, kt), lk, lk + AT_T64);
   };
 
   f16v ot[NDV];
@@ -130,16 +70,16 @@ __global__ __launch_bounds__(256, HD == 64 ? 3 : 2) void attn_bf16(const E* __re
   // the address of row key0 + qr, columns dv0 + 4p .. 4p+3
   const int t_qr = (lane & 15) >> 2, t_p = lane & 3, t_gp = (lane >> 4) & 1;
 
-  const int nkt = (Lk + A_KV - 1) / A_KV;
+  const int nkt = (Lk + AT_KV - 1) / AT_KV;
   stage(0, 0);
   for (int kt = 0; kt < nkt; ++kt) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of tile kt (asm LDS-DMA: not counted by the compiler)
     __syncthreads();
     if (kt + 1 < nkt) stage((kt + 1) & 1, kt + 1);
     const char* tk = smem + (kt & 1) * BUF;
-    const char* tv = tk + A_T64;
-    const char* tk32 = tk + 2 * A_T64;
-    const char* tv32 = tk32 + A_T32;
+    const char* tv = tk + AT_T64;
+    const char* tk32 = tk + 2 * AT_T64;
+    const char* tv32 = tk32 + AT_T32;
 
     // ---- S^T[key][q] - m for the two 32-key blocks
     // (A/B'd in round 2, bit-identical and time-neutral: chain heads as inline asm with an early-clobber result, which
@@ -152,17 +92,17 @@ __global__ __launch_bounds__(256, HD == 64 ? 3 : 2) void attn_bf16(const E* __re
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks) {
         u4v kf;
-        if (ks < 4) kf = *reinterpret_cast<const u4v*>(tk + row * 128 + (((2 * ks + hh) ^ ((row >> 1) & 7)) << 4));
-        else kf = *reinterpret_cast<const u4v*>(tk32 + row * 64 + (((2 * (ks - 4) + hh) ^ ((row >> 2) & 3)) << 4));
+        if (ks < 4) kf = *reinterpret_cast<const u4v*>(tk + I::k64(row, 2 * ks + hh));
+        else kf = *reinterpret_cast<const u4v*>(tk32 + I::k32(row, 2 * (ks - 4) + hh));
         st[kb] = Half16<E>::mfma32(kf, qf[ks], ks == 0 ? negm : st[kb]);
       }
     }
-    if (kt == nkt - 1 && (Lk & (A_KV - 1)) != 0) {  // ragged last tile: keys >= Lk contribute nothing
+    if (kt == nkt - 1 && (Lk & (AT_KV - 1)) != 0) {  // ragged last tile: keys >= Lk contribute nothing
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int key = kt * A_KV + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
+          const int key = kt * AT_KV + kb * 32 + (i & 3) + 8 * (i >> 2) + 4 * hh;
           if (key >= Lk) st[kb][i] = NEG_INF;
         }
     }
@@ -221,17 +161,8 @@ __global__ __launch_bounds__(256, HD == 64 ? 3 : 2) void attn_bf16(const E* __re
         for (int s2 = 0; s2 < 2; ++s2) {
           const int row0 = kb * 32 + 16 * s2 + 4 * hh + t_qr;
           const int row1 = row0 + 8;
-          const char *a0, *a1;
-          if (dvb < 2) {
-            a0 = tv + row0 * 128 + ((chunk ^ (((row0 >> 1) & 1) << 2)) << 4) + within;
-            a1 = tv + row1 * 128 + ((chunk ^ (((row1 >> 1) & 1) << 2)) << 4) + within;
-          } else {  // 4 consecutive 64-byte rows per 32-lane half = one 256-byte bank row: conflict-free as is
-            a0 = tv32 + row0 * 64 + (chunk << 4) + within;
-            a1 = tv32 + row1 * 64 + (chunk << 4) + within;
-          }
-          const bf4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf4v*)a0);
-          const bf4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf4v*)a1);
-          const u4v vf = __builtin_bit_cast(u4v, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+          const u4v vf = dvb < 2 ? read_tr16_pair(tv + I::v64(row0, chunk) + within, tv + I::v64(row1, chunk) + within)
+                                 : read_tr16_pair(tv32 + I::v32(row0, chunk) + within, tv32 + I::v32(row1, chunk) + within);
           ot[dvb] = Half16<E>::mfma32(vf, pb[kb][s2], ot[dvb]);
         }
     }
@@ -242,9 +173,8 @@ __global__ __launch_bounds__(256, HD == 64 ? 3 : 2) void attn_bf16(const E* __re
   const float inv = 1.0f / l_tot;
   const int qrow = q0 + r;
   if (qrow < Lq) {
-    // training: log2-domain log-sum-exp of the row's scaled scores, what the backward kernels rebuild P from (attn_bwd.hip)
-    if (LSE && hh == 0) lse[((size_t)s * heads + head) * Lq + qrow] = m_run + __log2f(l_tot);
-    E* op = o + ((size_t)s * Lq + qrow) * o_rs + head * HD;
+    if (LSE && hh == 0) *wg.lse_row(lse, Lq, qrow) = m_run + __log2f(l_tot);
+    E* op = wg.out_row(o, Lq, qrow, o_rs, HD);
 #pragma unroll
     for (int dvb = 0; dvb < NDV; ++dvb)
 #pragma unroll
@@ -384,8 +314,7 @@ __global__ __launch_bounds__(256) void attn_f32(const float* __restrict__ q, con
   }
 }
 
-// which bf16 / head_dim 64 structure nova_attn_fwd launches (per calling thread): 0 = 32x32x16 (attn_bf16 above),
-// 1 / 2 = 16x16x32 with 32 / 64 query rows per wave (attn16.hip), 3 / 4 = the same with the row sums on the matrix pipe, 5 = 4 software-pipelined (P V of tile t-1 beside the exponentials of tile t); -1 = the shipped choice
+// which bf16 / head_dim 64 structure nova_attn_fwd launches (per calling thread): an index into ATTN_FORMS (nova_internal.h); -1 = the shipped choice
 static thread_local int g_attn_variant = -1;
 int attn_set_variant(int v) {
   if (v < -1 || v > 5) return -1;
@@ -409,28 +338,22 @@ int attn_fwd(const void* q, const void* k, const void* v, void* o, int S, int he
   const int nq = (Lq + 127) / 128;
   if (S > 65535 || heads > 65535 || (long)nq * heads * S > 0x7fffffffL) return set_error(NOVA_ERR_SHAPE, "attn_fwd: grid too large");
   const float c = scale * 1.4426950408889634f;
-  dim3 grid(nq, heads, S), block(256), grid1((unsigned)((long)nq * heads * S));
+  dim3 grid(nq, heads, S), block(256);
   ProfScope prof(PROF_ATTN, 4.0 * S * heads * (double)Lq * Lk * hd, st);
   if (dtype_is16(dtype)) {
-    const float cl = q_prescaled ? 1.0f : c;
-    const int rev = walk_is_reverse() ? 1 : 0;
-    if (klim) return attn_fwd_m16(q, k, v, o, S, heads, Lq, Lk, hd, q_rs, kv_rs, o_rs, cl, dtype, st, kv_ss, lse, 32, true, false, klim);
-    if (attn_variant() != 0) {
-      // the shipped choice: 16x16x32, 32 query rows per wave, row sums on the matrix pipe, at every length. (64 rows per wave where
-      // 256-row workgroups tile the queries exactly is +1.3 .. 2 % standalone at L = 2560 - profiles/r03_attn_variants_ab.txt - but
-      // measured ~5 % SLOWER inside the generation step, where two lanes share the chip: attention / plain-GEMM rate 0.78 against 0.82
-      // over four bench runs; it also re-fetches 7 % more K / V, L2 hit 83 % against 91 %.)
-      const int av = attn_variant();
-      return attn_fwd_m16(q, k, v, o, S, heads, Lq, Lk, hd, q_rs, kv_rs, o_rs, cl, dtype, st, kv_ss, lse, (av & 1) && av != 5 ? 32 : 64, av >= 3,
-                          av == 5);
-    }
+    const AttnFwdArgs a{q, k, v, o, S, heads, Lq, Lk, hd, q_rs, kv_rs, o_rs, q_prescaled ? 1.0f : c, dtype, st, kv_ss, lse, klim};
+    // the shipped choice: 16x16x32, 32 query rows per wave, row sums on the matrix pipe, at every length. (64 rows per wave where
+    // 256-row workgroups tile the queries exactly is +1.3 .. 2 % standalone at L = 2560 - profiles/r03_attn_variants_ab.txt - but
+    // measured ~5 % SLOWER inside the generation step, where two lanes share the chip: attention / plain-GEMM rate 0.78 against 0.82
+    // over four bench runs; it also re-fetches 7 % more K / V, L2 hit 83 % against 91 %.)
+    const AttnForm f = ATTN_FORMS[attn_variant()];
+    if (klim || f.mfma == 16) return attn_fwd_m16(a, f);
     dispatch_half(dtype, [&](auto tag) {
       using E = decltype(tag);
-      const E *qq = (const E*)q, *kk = (const E*)k, *vv = (const E*)v;
-      if (lse && hd == 64) hipLaunchKernelGGL((attn_bf16<E, 64, true>), grid1, block, 0, st, qq, kk, vv, (E*)o, Lq, Lk, q_rs, kv_rs, o_rs, cl, heads, nq, rev, kv_ss, lse);
-      else if (lse) hipLaunchKernelGGL((attn_bf16<E, 96, true>), grid1, block, 0, st, qq, kk, vv, (E*)o, Lq, Lk, q_rs, kv_rs, o_rs, cl, heads, nq, rev, kv_ss, lse);
-      else if (hd == 64) hipLaunchKernelGGL((attn_bf16<E, 64, false>), grid1, block, 0, st, qq, kk, vv, (E*)o, Lq, Lk, q_rs, kv_rs, o_rs, cl, heads, nq, rev, kv_ss, lse);
-      else hipLaunchKernelGGL((attn_bf16<E, 96, false>), grid1, block, 0, st, qq, kk, vv, (E*)o, Lq, Lk, q_rs, kv_rs, o_rs, cl, heads, nq, rev, kv_ss, lse);
+      if (lse && hd == 64) attn_launch<E>(attn_bf16<E, 64, true>, 128, a);
+      else if (lse) attn_launch<E>(attn_bf16<E, 96, true>, 128, a);
+      else if (hd == 64) attn_launch<E>(attn_bf16<E, 64, false>, 128, a);
+      else attn_launch<E>(attn_bf16<E, 96, false>, 128, a);
       return 0;
     });
   } else {

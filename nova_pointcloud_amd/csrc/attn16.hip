@@ -15,18 +15,16 @@
 // cross-lane step); the bf16-packed S^T block pair IS the B operand of O^T = V^T P^T (k order inside the 32-key
 // contraction: element j < 4 from block 2kp, j >= 4 from block 2kp + 1, and the transposing V read fetches exactly
 // those rows); K/V 64-key tiles by LDS-DMA, double buffered, one barrier per tile.
-// LDS images (128-byte rows, 16-byte chunks): K chunk ^ ((row >> 1) & 7) - conflict-free for the 16-row ds_read_b128
-// fragment read; V chunk ^ (((row >> 1) & 3) << 1) - conflict-free for ds_read_b64_tr_b16 over 8 consecutive rows x 32 B.
+// Workgroup decode, LDS images (Layout16), staging, Q load, fragment reads, key mask and output store: attn_tile.h.
 #include <type_traits>
+#include "attn_tile.h"
 #include "common.h"
 #include "nova_internal.h"
 
 namespace nova {
 
 namespace {
-constexpr float NEG_INF16 = -__builtin_huge_valf();
-constexpr int B_KV = 64;           // keys per tile
-constexpr int B_T = B_KV * 128;    // one image: 8 KiB
+constexpr int B_KV = AT_KV, B_T = AT_T64;  // keys per tile, bytes of one 64-wide image
 
 // This file is compiled with -fno-honor-nans (Makefile): in IEEE mode hipcc canonicalises every MFMA result
 // before an fmaxf (one extra v_max per score, 16 of the loop's ~90 vector instructions per tile); without it plain
@@ -58,7 +56,7 @@ __device__ __forceinline__ float sum_over_g(float x) {
 }  // namespace
 
 // HD = 96 (d48w1536): a 64-wide image plus a 32-wide image (64-byte rows) per K / V tile, as attn.hip, so every LDS-DMA piece
-// stays row aligned; their swizzles: K32 chunk ^ s((row >> 2) & 3), s = (0, 2, 3, 1); V32 chunk ^ (((row >> 2) & 1) << 1).
+// stays row aligned.
 // MASK (the training forward of multi-frame models): a per-query key limit klim[Lq] - query i attends to keys [0, klim[i]), klim
 // non-decreasing and >= 1 - which is what the reference's block-causal frame mask is (embeddings.py:247-260: token i sees the tokens
 // of frames <= its own; the prefix counts as frame 0). Tiles are then walked in natural order (tile 0 holds an allowed key for
@@ -71,14 +69,9 @@ __device__ long long g_attn_clock[2 * 1024];
 #endif
 template <typename E, int HD, int NQB, bool LSE, bool SUMM, bool MASK = false>  // E: bf16_t / f16_t (same loads, LDS images and stores; MFMA form and pair packing differ)
 __global__ __launch_bounds__(256, (NQB == 2 && HD == 64) ? 3 : 2) void attn_bf16_m16(
-    const E* __restrict__ q, const E* __restrict__ k,
-                                                                         const E* __restrict__ v, E* __restrict__ o,
-                                                                         int Lq, int Lk, long q_rs, long kv_rs, long o_rs, float c,
-                                                                         int heads, int nq, int rev, long kv_ss, float* __restrict__ lse,
-                                                                         const int* __restrict__ klim = nullptr) {
-  constexpr int NDS = HD / 32, NDVB = HD / 16, RW = 16 * NQB;
-  constexpr int B_T32 = B_KV * 64;                                  // 32-wide image (HD = 96): 4 KiB
-  constexpr int BUF = 2 * B_T + (HD == 96 ? 2 * B_T32 : 0);         // [K64 | V64 | K32 | V32]
+    const E* __restrict__ q, const E* __restrict__ k, const E* __restrict__ v, E* __restrict__ o, int Lq, int Lk, long q_rs, long kv_rs, long o_rs,
+    float c, int heads, int nq, int rev, long kv_ss, float* __restrict__ lse, const int* __restrict__ klim = nullptr) {
+  constexpr int NDS = HD / 32, NDVB = HD / 16, RW = 16 * NQB, B_T32 = AT_T32, BUF = AT_BUF<HD>;
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
   const int tid = threadIdx.x, lane = tid & 63;
 #ifdef NOVA_CLOCK
@@ -86,71 +79,21 @@ __global__ __launch_bounds__(256, (NQB == 2 && HD == 64) ? 3 : 2) void attn_bf16
 #endif
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i = lane & 15, g = lane >> 4;
-  const int t = xcd_remap_dir(blockIdx.x, gridDim.x, rev != 0);
-  const int sh = t / nq, qt = t - sh * nq;
-  const int head = sh % heads, s = sh / heads;
-  const int q0 = qt * (4 * RW) + wid * RW;
-
-  const E* qb_ = q + (size_t)s * Lq * q_rs + head * HD;
-  const E* kb_ = k + (size_t)s * kv_ss + head * HD;
-  const E* vb_ = v + (size_t)s * kv_ss + head * HD;
+  const AttnWg wg(blockIdx.x, gridDim.x, rev, nq, heads, 4 * RW);
+  const int q0 = wg.row0 + wid * RW;
+  const E* qb_ = wg.seq(q, (long)Lq * q_rs, HD);
+  const E* kb_ = wg.seq(k, kv_ss, HD);
+  const E* vb_ = wg.seq(v, kv_ss, HD);
 
   // Q fragments, B operand of S^T = K Q^T: lane (i, g) holds Q[q0 + 16 qb + i][32 ds + 8 g + 0..7]
   u4v qf[NQB][NDS];
 #pragma unroll
-  for (int qb = 0; qb < NQB; ++qb) {
-    const int qrow = min(q0 + 16 * qb + i, Lq - 1);
-    const E* qp = qb_ + (size_t)qrow * q_rs + 8 * g;
-#pragma unroll
-    for (int ds = 0; ds < NDS; ++ds) qf[qb][ds] = *reinterpret_cast<const u4v*>(qp + 32 * ds);
-    if (c != 1.0f) {
-#pragma unroll
-      for (int ds = 0; ds < NDS; ++ds)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const f2v t = Half16<E>::unpack(qf[qb][ds][j]);
-          qf[qb][ds][j] = Half16<E>::pack(t[0] * c, t[1] * c);
-        }
-    }
-  }
+  for (int qb = 0; qb < NQB; ++qb) load_q<E, 32>(qb_ + (size_t)min(q0 + 16 * qb + i, Lq - 1) * q_rs + 8 * g, c, qf[qb]);
 
-  // staging (as attn.hip): wave w moves LDS-DMA pieces 2w, 2w+1 (8 rows x 128 B each) of the K and the V image
-  const uint32_t rowB = (uint32_t)kv_rs * 2u;
-  const int srow0 = (wid * 2) * 8 + (lane >> 3), srow1 = srow0 + 8, scp = lane & 7;
-  const uint32_t ck0 = (uint32_t)((scp ^ ((srow0 >> 1) & 7)) << 4), ck1 = (uint32_t)((scp ^ ((srow1 >> 1) & 7)) << 4);
-  const uint32_t cv0 = (uint32_t)((scp ^ (((srow0 >> 1) & 3) << 1)) << 4), cv1 = (uint32_t)((scp ^ (((srow1 >> 1) & 3) << 1)) << 4);
-  const uint32_t ko0 = srow0 * rowB + ck0, ko1 = srow1 * rowB + ck1, vo0 = srow0 * rowB + cv0, vo1 = srow1 * rowB + cv1;
-  // 32-wide images: wave w moves piece w (16 rows x 64 B) of each; source columns 64 .. 95 = byte 128 + 16 * chunk
-  const int srow32 = wid * 16 + (lane >> 2), scp32 = lane & 3;
-  const uint32_t ck32 = 128u + (uint32_t)((scp32 ^ ((0x78 >> (2 * ((srow32 >> 2) & 3))) & 3)) << 4);
-  const uint32_t cv32 = 128u + (uint32_t)((scp32 ^ (((srow32 >> 2) & 1) << 1)) << 4);
+  const KvStage<Layout16, HD> kv(wid, lane, kv_rs);
   auto stage = [&](int buf, int kt) {
     char* lk = smem + buf * BUF;
-    char* lv = lk + B_T;
-    const char* kbase = reinterpret_cast<const char*>(kb_) + (size_t)kt * B_KV * rowB;  // wave-uniform
-    const char* vbase = reinterpret_cast<const char*>(vb_) + (size_t)kt * B_KV * rowB;
-    const int lim = Lk - 1 - kt * B_KV;
-    if (lim >= B_KV - 1) {
-      glds16(kbase, ko0, lk + wid * 2048);
-      glds16(vbase, vo0, lv + wid * 2048);
-      glds16(kbase, ko1, lk + wid * 2048 + 1024);
-      glds16(vbase, vo1, lv + wid * 2048 + 1024);
-      if constexpr (HD == 96) {
-        glds16(kbase, srow32 * rowB + ck32, lk + 2 * B_T + wid * 1024);
-        glds16(vbase, srow32 * rowB + cv32, lk + 2 * B_T + B_T32 + wid * 1024);
-      }
-    } else {  // ragged tile: rows past Lk re-read the last valid row (their scores are masked to -inf)
-      const uint32_t r0 = (uint32_t)min(srow0, lim) * rowB, r1 = (uint32_t)min(srow1, lim) * rowB;
-      glds16(kbase, r0 + ck0, lk + wid * 2048);
-      glds16(vbase, r0 + cv0, lv + wid * 2048);
-      glds16(kbase, r1 + ck1, lk + wid * 2048 + 1024);
-      glds16(vbase, r1 + cv1, lv + wid * 2048 + 1024);
-      if constexpr (HD == 96) {
-        const uint32_t r32 = (uint32_t)min(srow32, lim) * rowB;
-        glds16(kbase, r32 + ck32, lk + 2 * B_T + wid * 1024);
-        glds16(vbase, r32 + cv32, lk + 2 * B_T + B_T32 + wid * 1024);
-      }
-    }
+    kv.stage(kv.tile(kb_, kt), kv.tile(vb_, kt), kv.last_row(Lk, kt), lk, lk + B_T);
   };
 
   f4v ot[NQB][NDVB], negm[NQB], lacc[NQB];  // lacc (SUMM): row sums of the bf16-rounded P from an all-ones V^T block
@@ -166,26 +109,14 @@ __global__ __launch_bounds__(256, (NQB == 2 && HD == 64) ? 3 : 2) void attn_bf16
     for (int d = 0; d < NDVB; ++d) ot[qb][d] = f4v{0.f, 0.f, 0.f, 0.f};
   }
 
-  // lane constants of the two read kinds
-  const uint32_t kx = (uint32_t)((i >> 1) & 7);                                    // K swizzle of rows 16 kb + i (independent of kb)
-  const uint32_t koff0 = (uint32_t)i * 128u + (((uint32_t)g ^ kx) << 4);           // d-step 0; d-step 1 flips chunk bit 2
-  const uint32_t koff1 = (uint32_t)i * 128u + ((((uint32_t)g + 4u) ^ kx) << 4);
-  const int t_q = (lane & 15) >> 2, t_p = lane & 3;
-  const uint32_t vrow = (uint32_t)(4 * g + t_q);                                   // + 32 kp (+ 16 for the high half): swizzle unchanged
-  const uint32_t vx = ((vrow >> 1) & 3u) << 1;
-  uint32_t voff[NDVB];  // dvb < 4: inside the 64-wide V image; dvb 4, 5: inside the 32-wide one (64-byte rows)
-#pragma unroll
-  for (int dvb = 0; dvb < NDVB; ++dvb)
-    voff[dvb] = dvb < 4 ? vrow * 128u + ((((uint32_t)(2 * dvb + (t_p >> 1))) ^ vx) << 4) + 8u * (t_p & 1)
-                        : vrow * 64u + ((((uint32_t)(2 * (dvb - 4) + (t_p >> 1))) ^ (((vrow >> 2) & 1u) << 1)) << 4) + 8u * (t_p & 1);
-  const uint32_t koff2 = (uint32_t)i * 64u + (((uint32_t)g ^ (uint32_t)((0x78 >> (2 * ((i >> 2) & 3))) & 3)) << 4);  // d-step 2: the 32-wide K image
+  const Read16<HD> rd(lane);
 
   int kl[NQB];  // MASK: this lane's key limit per query block
   int k_end = Lk;
   if constexpr (MASK) {
 #pragma unroll
     for (int qb = 0; qb < NQB; ++qb) kl[qb] = min(klim[min(q0 + 16 * qb + i, Lq - 1)], Lk);
-    k_end = min(klim[min(qt * (4 * RW) + 4 * RW - 1, Lq - 1)], Lk);  // the workgroup's last row has its largest limit
+    k_end = min(klim[min(wg.row0 + 4 * RW - 1, Lq - 1)], Lk);  // the workgroup's last row has its largest limit
   }
   const int nkt = (k_end + B_KV - 1) / B_KV;
   // Tile order: the (possibly ragged) LAST tile goes first, as a peeled step (softmax does not care about key order), so the
@@ -224,10 +155,7 @@ __global__ __launch_bounds__(256, (NQB == 2 && HD == 64) ? 3 : 2) void attn_bf16
     auto pv = [&](int kp) {
 #pragma unroll
       for (int dvb = 0; dvb < NDVB; ++dvb) {
-        const char* a0 = dvb < 4 ? tv + kp * 4096 + voff[dvb] : tv32 + kp * 2048 + voff[dvb];
-        const bf4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf4v*)a0);
-        const bf4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf4v*)(a0 + (dvb < 4 ? 2048 : 1024)));
-        const u4v vf = __builtin_bit_cast(u4v, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+        const u4v vf = rd.vfrag(tv, kp, dvb, tv32);
 #pragma unroll
         for (int qb = 0; qb < NQB; ++qb) ot[qb][dvb] = Half16<E>::mfma16(vf, pb[qb][kp], ot[qb][dvb]);
       }
@@ -246,8 +174,7 @@ __global__ __launch_bounds__(256, (NQB == 2 && HD == 64) ? 3 : 2) void attn_bf16
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
           const int kb = kb2 + kk;
-          const u4v kf = ds < 2 ? *reinterpret_cast<const u4v*>(tk + kb * 2048 + (ds == 0 ? koff0 : koff1))
-                                : *reinterpret_cast<const u4v*>(tk32 + kb * 1024 + koff2);
+          const u4v kf = rd.kfrag(tk, kb, ds, tk32);
 #pragma unroll
           for (int qb = 0; qb < NQB; ++qb)
             st[qb][kb] = Half16<E>::mfma16(kf, qf[qb][ds], ds == 0 ? negm[qb] : st[qb][kb]);
@@ -261,31 +188,13 @@ __global__ __launch_bounds__(256, (NQB == 2 && HD == 64) ? 3 : 2) void attn_bf16
       }
     }
     if constexpr (MASK) {  // every tile: keys at or past the query's limit (which is <= Lk) contribute nothing
-#pragma unroll
-      for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int key = tile * B_KV + 16 * kb + 4 * g + r;
-#pragma unroll
-          for (int qb = 0; qb < NQB; ++qb) st[qb][kb][r] = key < kl[qb] ? st[qb][kb][r] : NEG_INF16;
-        }
+      mask_keys16(st, tile, g, [&](int qb) { return kl[qb]; });
     } else if constexpr (FIRST) {
-      if ((Lk & (B_KV - 1)) != 0) {  // ragged tile: keys >= Lk contribute nothing
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int key = tile * B_KV + 16 * kb + 4 * g + r;
-            if (key >= Lk) {
-#pragma unroll
-              for (int qb = 0; qb < NQB; ++qb) st[qb][kb][r] = NEG_INF16;
-            }
-          }
-      }
+      if ((Lk & (B_KV - 1)) != 0) mask_keys16(st, tile, g, [&](int) { return Lk; });  // ragged tile: keys >= Lk contribute nothing
     }
     // ---- online softmax. Lane-local maxima decide (wave-uniformly) whether anything moves; the reduction across the four
     // lanes of a query only runs inside the branch.
-    float mx[NQB], mall = NEG_INF16;
+    float mx[NQB], mall = NEG_INF;
 #pragma unroll
     for (int qb = 0; qb < NQB; ++qb) {
       mx[qb] = max16(st[qb]);
@@ -357,20 +266,8 @@ __global__ __launch_bounds__(256, (NQB == 2 && HD == 64) ? 3 : 2) void attn_bf16
 
   // ---- finalize: lane (i, g) holds O[q0 + 16 qb + i][16 dvb + 4 g + 0..3]
 #pragma unroll
-  for (int qb = 0; qb < NQB; ++qb) {
-    const float l_tot = SUMM ? lacc[qb][0] : sum_over_g(l_run[qb]);
-    const float inv = 1.0f / l_tot;
-    const int qrow = q0 + 16 * qb + i;
-    if (qrow < Lq) {
-      if (LSE && g == 0) lse[((size_t)s * heads + head) * Lq + qrow] = m_run[qb] + __log2f(l_tot);
-      E* op = o + ((size_t)s * Lq + qrow) * o_rs + head * HD + 4 * g;
-#pragma unroll
-      for (int dvb = 0; dvb < NDVB; ++dvb) {
-        u2v pk = {Half16<E>::pack(ot[qb][dvb][0] * inv, ot[qb][dvb][1] * inv), Half16<E>::pack(ot[qb][dvb][2] * inv, ot[qb][dvb][3] * inv)};
-        *reinterpret_cast<u2v*>(op + 16 * dvb) = pk;
-      }
-    }
-  }
+  for (int qb = 0; qb < NQB; ++qb)
+    store_block16<E, NDVB, LSE>(wg, ot[qb], SUMM ? lacc[qb][0] : sum_over_g(l_run[qb]), m_run[qb], q0 + 16 * qb + i, g, o, Lq, o_rs, lse);
 #ifdef NOVA_CLOCK
   if (tid == 0) {
     g_attn_clock[2 * (blockIdx.x & 1023)] = __builtin_amdgcn_s_memtime() - ck_t0;
@@ -401,13 +298,11 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_m16p(const E* __restrict__ q
 #endif
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i = lane & 15, g = lane >> 4;
-  const int t = xcd_remap_dir(blockIdx.x, gridDim.x, rev != 0);
-  const int sh = t / nq, qt = t - sh * nq;
-  const int head = sh % heads, s = sh / heads;
-  const int q0 = qt * (4 * RW) + wid * RW;
-  const E* qb_ = q + (size_t)s * Lq * q_rs + head * HD;
-  const E* kb_ = k + (size_t)s * kv_ss + head * HD;
-  const E* vb_ = v + (size_t)s * kv_ss + head * HD;
+  const AttnWg wg(blockIdx.x, gridDim.x, rev, nq, heads, 4 * RW);
+  const int q0 = wg.row0 + wid * RW;
+  const E* qb_ = wg.seq(q, (long)Lq * q_rs, HD);
+  const E* kb_ = wg.seq(k, kv_ss, HD);
+  const E* vb_ = wg.seq(v, kv_ss, HD);
 
   // The wave's 64 Q rows live in its own 8 KiB of LDS (K's image and swizzle; written once, read back as B fragments at the
   // top of every tile): 32 registers that the exp / P V block of the pipeline needs more than the score block does.
@@ -415,34 +310,19 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_m16p(const E* __restrict__ q
 #pragma unroll
   for (int qb = 0; qb < NQB; ++qb) {
     const int row = 16 * qb + i;
-    const int qrow = min(q0 + row, Lq - 1);
-    const E* qp = qb_ + (size_t)qrow * q_rs + 8 * g;
+    const E* qp = qb_ + (size_t)min(q0 + row, Lq - 1) * q_rs + 8 * g;
 #pragma unroll
     for (int ds = 0; ds < NDS; ++ds) {
-      u4v f = *reinterpret_cast<const u4v*>(qp + 32 * ds);
-      if (c != 1.0f) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const f2v t = Half16<E>::unpack(f[j]);
-          f[j] = Half16<E>::pack(t[0] * c, t[1] * c);
-        }
-      }
-      *reinterpret_cast<u4v*>(qs + row * 128 + (((4 * ds + g) ^ ((row >> 1) & 7)) << 4)) = f;
+      u4v f[1];
+      load_q<E, 0>(qp + 32 * ds, c, f);
+      *reinterpret_cast<u4v*>(qs + Image<Layout16>::k64(row, 4 * ds + g)) = f[0];
     }
   }
 
-  const uint32_t rowB = (uint32_t)kv_rs * 2u;
-  const int srow0 = (wid * 2) * 8 + (lane >> 3), srow1 = srow0 + 8, scp = lane & 7;
-  const uint32_t ck0 = (uint32_t)((scp ^ ((srow0 >> 1) & 7)) << 4), ck1 = (uint32_t)((scp ^ ((srow1 >> 1) & 7)) << 4);
-  const uint32_t cv0 = (uint32_t)((scp ^ (((srow0 >> 1) & 3) << 1)) << 4), cv1 = (uint32_t)((scp ^ (((srow1 >> 1) & 3) << 1)) << 4);
-  // one image (K or V, chosen by the wave-uniform base / chunk offsets) of tile kt into LDS at dst
-  auto stage1 = [&](const E* src, char* dst, int kt, uint32_t c0, uint32_t c1) {
-    const char* base = reinterpret_cast<const char*>(src) + (size_t)kt * B_KV * rowB;
-    const int lim = Lk - 1 - kt * B_KV;
-    const uint32_t r0 = (uint32_t)min(srow0, lim) * rowB, r1 = (uint32_t)min(srow1, lim) * rowB;  // rows past Lk re-read the last valid row
-    glds16(base, r0 + c0, dst + wid * 2048);
-    glds16(base, r1 + c1, dst + wid * 2048 + 1024);
-  };
+  const KvStage<Layout16, HD> kv(wid, lane, kv_rs);
+  // one image (K or V) of tile kt into LDS at dst
+  auto stage_k = [&](char* dst, int kt) { kv.stage_k64(kv.tile(kb_, kt), kv.last_row(Lk, kt), dst); };
+  auto stage_v = [&](char* dst, int kt) { kv.stage_v64(kv.tile(vb_, kt), kv.last_row(Lk, kt), dst); };
 
   f4v ot[NQB][NDVB], lacc[NQB];
   float m_run[NQB];
@@ -454,15 +334,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_m16p(const E* __restrict__ q
 #pragma unroll
     for (int d = 0; d < NDVB; ++d) ot[qb][d] = f4v{0.f, 0.f, 0.f, 0.f};
   }
-  const uint32_t kx = (uint32_t)((i >> 1) & 7);
-  const uint32_t koff0 = (uint32_t)i * 128u + (((uint32_t)g ^ kx) << 4);
-  const uint32_t koff1 = (uint32_t)i * 128u + ((((uint32_t)g + 4u) ^ kx) << 4);
-  const int t_q = (lane & 15) >> 2, t_p = lane & 3;
-  const uint32_t vrow = (uint32_t)(4 * g + t_q);
-  const uint32_t vx = ((vrow >> 1) & 3u) << 1;
-  uint32_t voff[NDVB];
-#pragma unroll
-  for (int dvb = 0; dvb < NDVB; ++dvb) voff[dvb] = vrow * 128u + ((((uint32_t)(2 * dvb + (t_p >> 1))) ^ vx) << 4) + 8u * (t_p & 1);
+  const Read16<HD> rd(lane);
 
   const int nkt = (Lk + B_KV - 1) / B_KV;
 
@@ -478,7 +350,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_m16p(const E* __restrict__ q
 #pragma unroll
     for (int qb = 0; qb < NQB; ++qb) {
 #pragma unroll
-      for (int ds = 0; ds < NDS; ++ds) qf[qb][ds] = *reinterpret_cast<const u4v*>(qs + qb * 2048 + (ds == 0 ? koff0 : koff1));
+      for (int ds = 0; ds < NDS; ++ds) qf[qb][ds] = rd.kfrag(qs, qb, ds);
       float nm = -m_run[qb];
       asm volatile("" : "+v"(nm));  // rebuilt per tile: the 4-register -m block is not carried through the exp / P V block
       negm[qb] = f4v{nm, nm, nm, nm};
@@ -487,25 +359,14 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_m16p(const E* __restrict__ q
     for (int kb = 0; kb < 4; ++kb) {
 #pragma unroll
       for (int ds = 0; ds < NDS; ++ds) {
-        const u4v kf = *reinterpret_cast<const u4v*>(tk + kb * 2048 + (ds == 0 ? koff0 : koff1));
+        const u4v kf = rd.kfrag(tk, kb, ds);
 #pragma unroll
         for (int qb = 0; qb < NQB; ++qb)
           st[qb][kb] = Half16<E>::mfma16(kf, qf[qb][ds], ds == 0 ? negm[qb] : st[qb][kb]);
       }
     }
     if constexpr (FIRST) {
-      if ((Lk & (B_KV - 1)) != 0) {  // ragged tile: keys >= Lk contribute nothing
-#pragma unroll
-        for (int kb = 0; kb < 4; ++kb)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int key = (nkt - 1) * B_KV + 16 * kb + 4 * g + r;
-            if (key >= Lk) {
-#pragma unroll
-              for (int qb = 0; qb < NQB; ++qb) st[qb][kb][r] = NEG_INF16;
-            }
-          }
-      }
+      if ((Lk & (B_KV - 1)) != 0) mask_keys16(st, nkt - 1, g, [&](int) { return Lk; });  // ragged tile: keys >= Lk contribute nothing
     }
     float mx[NQB], mall = 0.f;
 #pragma unroll
@@ -552,10 +413,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_m16p(const E* __restrict__ q
   };
   // O^T += V^T(tile) P^T for one (kp, dvb): one transposed fragment, NQB MFMAs
   auto pv_step = [&](const char* tv, const u4v (&pend)[NQB][2], int kp, int dvb) {
-    const char* a0 = tv + kp * 4096 + voff[dvb];
-    const bf4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf4v*)a0);
-    const bf4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((__attribute__((address_space(3))) bf4v*)(a0 + 2048));
-    const u4v vf = __builtin_bit_cast(u4v, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+    const u4v vf = rd.vfrag(tv, kp, dvb);
 #pragma unroll
     for (int qb = 0; qb < NQB; ++qb) ot[qb][dvb] = Half16<E>::mfma16(vf, pend[qb][kp], ot[qb][dvb]);
   };
@@ -568,11 +426,11 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_m16p(const E* __restrict__ q
   auto tile_of = [&](int step) { return step == 0 ? nkt - 1 : step - 1; };
   // ---- prologue: step 0 (the last tile) up to its packed P. Ring: K(step) in buffer step & 1, V(step) likewise; V lags K
   // by one step (staged with K(step + 1), read during step + 1).
-  stage1(kb_, smem, tile_of(0), ck0, ck1);
+  stage_k(smem, tile_of(0));
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (nkt > 1) stage1(kb_, smem + 2 * B_T, tile_of(1), ck0, ck1);
-  stage1(vb_, smem + B_T, tile_of(0), cv0, cv1);
+  if (nkt > 1) stage_k(smem + 2 * B_T, tile_of(1));
+  stage_v(smem + B_T, tile_of(0));
   {
     f4v st[NQB][4];
     score_block(std::true_type{}, 0, st, pbp);
@@ -586,8 +444,8 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_m16p(const E* __restrict__ q
   for (int j = 1; j < nkt; ++j) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (j + 1 < nkt) stage1(kb_, smem + ((j + 1) & 1) * 2 * B_T, j, ck0, ck1);  // tile_of(j + 1) = j
-    stage1(vb_, smem + (j & 1) * 2 * B_T + B_T, j - 1, cv0, cv1);               // tile_of(j) = j - 1
+    if (j + 1 < nkt) stage_k(smem + ((j + 1) & 1) * 2 * B_T, j);  // tile_of(j + 1) = j
+    stage_v(smem + (j & 1) * 2 * B_T + B_T, j - 1);               // tile_of(j) = j - 1
     const char* tv = smem + ((j + 1) & 1) * 2 * B_T + B_T;  // V(step j - 1)
     f4v st[NQB][4];
     score_block(std::false_type{}, j & 1, st, pbp);
@@ -619,20 +477,7 @@ __global__ __launch_bounds__(256, 2) void attn_bf16_m16p(const E* __restrict__ q
   }
 
 #pragma unroll
-  for (int qb = 0; qb < NQB; ++qb) {
-    const float l_tot = lacc[qb][0];
-    const float inv = 1.0f / l_tot;
-    const int qrow = q0 + 16 * qb + i;
-    if (qrow < Lq) {
-      if (LSE && g == 0) lse[((size_t)s * heads + head) * Lq + qrow] = m_run[qb] + __log2f(l_tot);
-      E* op = o + ((size_t)s * Lq + qrow) * o_rs + head * HD + 4 * g;
-#pragma unroll
-      for (int dvb = 0; dvb < NDVB; ++dvb) {
-        u2v pk = {Half16<E>::pack(ot[qb][dvb][0] * inv, ot[qb][dvb][1] * inv), Half16<E>::pack(ot[qb][dvb][2] * inv, ot[qb][dvb][3] * inv)};
-        *reinterpret_cast<u2v*>(op + 16 * dvb) = pk;
-      }
-    }
-  }
+  for (int qb = 0; qb < NQB; ++qb) store_block16<E, NDVB, LSE>(wg, ot[qb], lacc[qb][0], m_run[qb], q0 + 16 * qb + i, g, o, Lq, o_rs, lse);
 #ifdef NOVA_CLOCK
   if (tid == 0) {
     g_attn_clock[2 * (blockIdx.x & 1023)] = __builtin_amdgcn_s_memtime() - ck_t0;
@@ -649,51 +494,29 @@ extern "C" int nova_debug_attn_clock(long long* out, int n) {
 namespace nova {
 #endif
 
-// rows_per_wave 32 or 64 (head_dim 64; head_dim 96 runs the 32-row form with MFMA row sums whatever is asked); dtype NOVA_BF16 or NOVA_F16 (attn_fwd in attn.hip checks shapes and strides before it dispatches here)
-int attn_fwd_m16(const void* q, const void* k, const void* v, void* o, int S, int heads, int Lq, int Lk, int hd, long q_rs, long kv_rs,
-                 long o_rs, float cl, int dtype, hipStream_t st, long kv_ss, float* lse, int rows_per_wave, bool sum_on_mfma, bool pipelined,
-                 const int* klim) {
-  if (klim) {  // the masked training forward: built in the shipped form with the log-sum-exp output
-    if (!lse) return set_error(NOVA_ERR_ARG, "attn_fwd: a key-limit mask comes with the training forward (log-sum-exp output)");
-    const int nqm = (Lq + 127) / 128;
-    dim3 blk(256), grd((unsigned)((long)nqm * heads * S));
-    const int rv = walk_is_reverse() ? 1 : 0;
-    dispatch_half(dtype, [&](auto tag) {
-      using E = decltype(tag);
-      if (hd == 64) hipLaunchKernelGGL((attn_bf16_m16<E, 64, 2, true, true, true>), grd, blk, 0, st, (const E*)q, (const E*)k, (const E*)v, (E*)o, Lq, Lk, q_rs, kv_rs, o_rs, cl, heads, nqm, rv, kv_ss, lse, klim);
-      else hipLaunchKernelGGL((attn_bf16_m16<E, 96, 2, true, true, true>), grd, blk, 0, st, (const E*)q, (const E*)k, (const E*)v, (E*)o, Lq, Lk, q_rs, kv_rs, o_rs, cl, heads, nqm, rv, kv_ss, lse, klim);
-      return 0;
-    });
-    return check_launch("attn_fwd_m16 (masked)");
-  }
-  const int rw = (rows_per_wave == 64 && hd == 64) ? 64 : 32;
-  const int nq = (Lq + 4 * rw - 1) / (4 * rw);
-  if ((long)nq * heads * S > 0x7fffffffL) return set_error(NOVA_ERR_SHAPE, "attn_fwd: grid too large");
-  dim3 block(256), grid((unsigned)((long)nq * heads * S));
-  const int rev = walk_is_reverse() ? 1 : 0;
-  dispatch_half(dtype, [&](auto tag) {
+// head_dim 96 and the masked training forward are built in the shipped form only: 32 rows per wave, row sums on the matrix pipe
+template <typename E, bool LSE> static void launch_m16(const AttnFwdArgs& a, const AttnForm& f) {
+  if (a.klim) {
+    if constexpr (LSE) {
+      if (a.hd == 64) attn_launch<E>(attn_bf16_m16<E, 64, 2, true, true, true>, 128, a, a.klim);
+      else attn_launch<E>(attn_bf16_m16<E, 96, 2, true, true, true>, 128, a, a.klim);
+    }
+  } else if (a.hd == 96) attn_launch<E>(attn_bf16_m16<E, 96, 2, LSE, true>, 128, a, a.klim);
+  else if (f.pipelined) attn_launch<E>(attn_bf16_m16p<E, LSE>, 256, a);
+  else if (f.nqb == 2 && !f.summ) attn_launch<E>(attn_bf16_m16<E, 64, 2, LSE, false>, 128, a, a.klim);
+  else if (f.nqb == 2) attn_launch<E>(attn_bf16_m16<E, 64, 2, LSE, true>, 128, a, a.klim);
+  else if (!f.summ) attn_launch<E>(attn_bf16_m16<E, 64, 4, LSE, false>, 256, a, a.klim);
+  else attn_launch<E>(attn_bf16_m16<E, 64, 4, LSE, true>, 256, a, a.klim);
+}
+
+int attn_fwd_m16(const AttnFwdArgs& a, AttnForm f) {
+  dispatch_half(a.dtype, [&](auto tag) {
     using E = decltype(tag);
-    const E *qq = (const E*)q, *kk = (const E*)k, *vv = (const E*)v;
-    E* oo = (E*)o;
-#define NOVA_A16(NQB_, SUMM_)                                                                                                       \
-  do {                                                                                                                             \
-    if (lse) hipLaunchKernelGGL((attn_bf16_m16<E, 64, NQB_, true, SUMM_>), grid, block, 0, st, qq, kk, vv, oo, Lq, Lk, q_rs, kv_rs, o_rs, cl, heads, nq, rev, kv_ss, lse, nullptr); \
-    else hipLaunchKernelGGL((attn_bf16_m16<E, 64, NQB_, false, SUMM_>), grid, block, 0, st, qq, kk, vv, oo, Lq, Lk, q_rs, kv_rs, o_rs, cl, heads, nq, rev, kv_ss, lse);    \
-  } while (0)
-    if (hd == 96) {  // built in the shipped form only: 32 rows per wave, row sums on the matrix pipe
-      if (lse) hipLaunchKernelGGL((attn_bf16_m16<E, 96, 2, true, true>), grid, block, 0, st, qq, kk, vv, oo, Lq, Lk, q_rs, kv_rs, o_rs, cl, heads, nq, rev, kv_ss, lse);
-      else hipLaunchKernelGGL((attn_bf16_m16<E, 96, 2, false, true>), grid, block, 0, st, qq, kk, vv, oo, Lq, Lk, q_rs, kv_rs, o_rs, cl, heads, nq, rev, kv_ss, lse);
-    } else if (pipelined) {
-      if (lse) hipLaunchKernelGGL((attn_bf16_m16p<E, true>), grid, block, 0, st, qq, kk, vv, oo, Lq, Lk, q_rs, kv_rs, o_rs, cl, heads, nq, rev, kv_ss, lse);
-      else hipLaunchKernelGGL((attn_bf16_m16p<E, false>), grid, block, 0, st, qq, kk, vv, oo, Lq, Lk, q_rs, kv_rs, o_rs, cl, heads, nq, rev, kv_ss, lse);
-    } else if (rw == 32 && !sum_on_mfma) NOVA_A16(2, false);
-    else if (rw == 32) NOVA_A16(2, true);
-    else if (!sum_on_mfma) NOVA_A16(4, false);
-    else NOVA_A16(4, true);
-#undef NOVA_A16
+    if (a.lse) launch_m16<E, true>(a, f);
+    else launch_m16<E, false>(a, f);
     return 0;
   });
-  return check_launch("attn_fwd_m16");
+  return check_launch(a.klim ? "attn_fwd_m16 (masked)" : "attn_fwd_m16");
 }
 
 }  // namespace nova

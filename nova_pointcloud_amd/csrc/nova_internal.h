@@ -87,12 +87,39 @@ bool walk_is_reverse();
 int attn_fwd(const void* q, const void* k, const void* v, void* o, int S, int heads, int Lq, int Lk, int hd,
              long q_row_stride, long kv_row_stride, long o_row_stride, float scale, int dtype, hipStream_t st,
              bool q_prescaled = false, long kv_seq_stride = 0, float* lse = nullptr, const int* klim = nullptr);
-// attn16.hip: the same attention on the 16x16x32 MFMA shape (bf16, head_dim 64), 32 or 64 query rows per wave
-int attn_fwd_m16(const void* q, const void* k, const void* v, void* o, int S, int heads, int Lq, int Lk, int hd, long q_rs, long kv_rs,
-                 long o_rs, float cl, int dtype, hipStream_t st, long kv_ss, float* lse, int rows_per_wave, bool sum_on_mfma, bool pipelined = false,
-                 const int* klim = nullptr);  // klim [Lq]: optional per-query key limit (training forward, block-causal frame mask)
+// One 16-bit forward call as its kernels take it: cl = what q still has to be multiplied by (1 when its producer folded
+// scale * log2 e in), klim [Lq] the optional per-query key limit (training forward, block-causal frame mask).
+struct AttnFwdArgs {
+  const void *q, *k, *v;
+  void* o;
+  int S, heads, Lq, Lk, hd;
+  long q_rs, kv_rs, o_rs;
+  float cl;
+  int dtype;
+  hipStream_t st;
+  long kv_ss;
+  float* lse;
+  const int* klim;
+};
+// Every 16-bit forward kernel takes the same leading arguments (a masked one: klim after them), named here once. One workgroup
+// = rows_per_wg query rows of one (sequence, head); attn_fwd has checked the grid at 128 rows, the smallest.
+template <typename E, typename K, typename... X> inline void attn_launch(K kernel, int rows_per_wg, const AttnFwdArgs& a, X... extra) {
+  const int nq = (a.Lq + rows_per_wg - 1) / rows_per_wg;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((long)nq * a.heads * a.S)), dim3(256), 0, a.st, (const E*)a.q, (const E*)a.k, (const E*)a.v, (E*)a.o,
+                     a.Lq, a.Lk, a.q_rs, a.kv_rs, a.o_rs, a.cl, a.heads, nq, walk_is_reverse() ? 1 : 0, a.kv_ss, a.lse, extra...);
+}
+// Which head_dim 64 structure a variant number (nova_debug_set_attn_variant) means: the MFMA shape (32 = attn_bf16 in attn.hip,
+// 16 = attn16.hip), 16-query blocks per wave, row sums on the matrix pipe, software-pipelined (P V of tile t-1 beside the
+// exponentials of tile t). head_dim 96 and the masked forward are built as ATTN_FORMS[3] only, whatever is asked of the 16x16 family.
+struct AttnForm {
+  int mfma, nqb;
+  bool summ, pipelined;
+};
+constexpr AttnForm ATTN_FORMS[6] = {{32, 2, false, false}, {16, 2, false, false}, {16, 4, false, false},
+                                    {16, 2, true, false},  {16, 4, true, false},  {16, 4, true, true}};
 // 16x16x32, 32 rows per wave, row sums on the matrix pipe: +8 .. 11 % over variant 0 at every L measured (profiles/r03_attn_variants_ab.txt)
 constexpr int NOVA_ATTN_DEFAULT_VARIANT = 3;
+int attn_fwd_m16(const AttnFwdArgs& a, AttnForm f);  // attn16.hip; attn_fwd checks shapes, strides and the grid before it dispatches here
 int attn_set_variant(int v);  // -1 default, 0 .. 5 (attn.hip); -1 returned for other values
 int attn_variant();
 // attn_bwd.hip (bf16, head_dim 64 / 96): gradients of the attention above from q (pre-scaled by scale * log2 e), k, v, the
