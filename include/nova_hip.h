@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NOVA_HIP_VERSION 405 /* still 0.4.5 (tests/test_pointset_fps.py pins the number; a library without the new symbols fails to bind, loudly): nova_pointset_nearest_match, nova_pointset_nearest_match_bwd (nearest match with indices and its backward, for the Chamfer-type training losses); nova_pointset_knn (exact k nearest neighbours of a cloud set); nova_pointset_assignment, nova_pointset_assignment_state_bytes, nova_pointset_assignment_rounds (optimal assignment of two clouds by a batched integer auction: the exact EMD on the GPU); 0.4.5: nova_pointset_farthest_point_sample (farthest point sampling of a cloud set, to bring sets to a common point count); 0.4.4: nova_pointset_occupancy_grid (occupancy grid of a cloud set for the JSD metric); 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
+#define NOVA_HIP_VERSION 405 /* still 0.4.5 (tests/test_pointset_fps.py pins the number; a library without the new symbols fails to bind, loudly): nova_pointset_kernel_interpolate_stats, nova_pointset_kernel_interpolate_bwd (the interpolation forward with its statistics and its backward, for nova_pointcloud_amd.sampling); nova_pointset_nearest_match, nova_pointset_nearest_match_bwd (nearest match with indices and its backward, for the Chamfer-type training losses); nova_pointset_knn (exact k nearest neighbours of a cloud set); nova_pointset_assignment, nova_pointset_assignment_state_bytes, nova_pointset_assignment_rounds (optimal assignment of two clouds by a batched integer auction: the exact EMD on the GPU); 0.4.5: nova_pointset_farthest_point_sample (farthest point sampling of a cloud set, to bring sets to a common point count); 0.4.4: nova_pointset_occupancy_grid (occupancy grid of a cloud set for the JSD metric); 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
 
 typedef enum { NOVA_F32 = 0, NOVA_BF16 = 1, NOVA_F16 = 2 } nova_dtype;
 typedef enum { NOVA_ACT_NONE = 0, NOVA_ACT_GELU_ERF = 1, NOVA_ACT_SILU = 2 } nova_act;
@@ -416,6 +416,52 @@ int nova_pointset_knn(const float* x, const float* y, int* idx, float* d2, int S
 #define NOVA_INTERP_MAX_CHANNELS 8
 int nova_pointset_kernel_interpolate(const float* q, const float* p, const float* v, float* out,
                                      int S, int T, int N, int C, float scale, void* stream);
+
+/* The same forward with its statistics, and its backward: the gradient of the interpolation with respect to the queries,
+ * the source points and the values, which the reference takes by autograd through feature_aware_interpolation
+ * (transformer_pointcloud_nova.py:128-152; adaptive_sampling, :92-97, is called without no_grad inside
+ * generate_pointcloud_autoregressive, :641-700, so with use_autoregressive the training gradient reaches the points through
+ * softmax(-cdist) and the [S, T, N, 3] product, both kept alive for the backward). Neither pass stores anything of size T N.
+ * nova_pointset_kernel_interpolate_stats: nova_pointset_kernel_interpolate, bit for bit (the same scan and merge), which
+ *   also stores m[s, i] = M and l[s, i] = L of that definition (float32 [S, T]): M the smallest d_j of the row, L the merged
+ *   weight sum (L >= 1: the nearest source has weight exactly 1).
+ * nova_pointset_kernel_interpolate_bwd: from g [S, T, C] = dLoss/dout, the forward's inputs, its out and its m, l:
+ *   gq [S, T, 3], gp [S, N, 3] and gv [S, N, C] (float32). The temperature gets no gradient. For query i and source j of one
+ *   cloud, every operation rounded once to float32 and nothing fused that is not written as fmaf:
+ *     e_k     = q_i[k] - p_j[k]                             per axis
+ *     d       = sqrtf(sqdist3(q_i, p_j))                    the forward's distance, so M_i <= d holds exactly
+ *     w       = exp2f((M_i - d) * scale)                    as the forward (v_exp_f32)
+ *     r_i     = 1 / L_i                                     one IEEE division per query
+ *     P       = w * r_i                                     1 / L is applied as a PRODUCT with the rounded quotient r_i
+ *     delta_i = fmaf(g_i[C-1], out_i[C-1], ... fmaf(g_i[1], out_i[1], g_i[0] * out_i[0]))      ascending channel
+ *     dot     = fmaf(g_i[C-1], v_j[C-1], ... fmaf(g_i[1], v_j[1], g_i[0] * v_j[0]))            ascending channel; the kernels
+ *               run both chains over their rung of 3, 4 or 8 channels with zeros past C, which adds nothing (but turns a sum of -0 into +0)
+ *     kappa   = scale * 0.693147180559945309f               (= 1 / temperature; scale == 0 gives exactly 0 gradient through d)
+ *     f       = (kappa * (P * (dot - delta_i))) * rcp(d)    rcp the hardware's v_rcp_f32 (1 ulp); f = 0 where d == 0: the
+ *               subgradient convention of nova_pointset_nearest_match_bwd, coincident points give no gradient and no NaN
+ *               (the queries of feature_aware_interpolation ARE source points, so d == 0 occurs for every query)
+ *   delta_i is formed in the prologue of each of the two kernels, by this one expression; there is no pass for it.
+ *   gq[i, k]: the forward's workgroup shape (256 threads, 64 queries, one per lane in all four waves, wave w taking the
+ *     64-source chunks w, w + 4, ... in ascending index): a_w[k] = fmaf(-f, e_k, a_w[k]) from +0, then
+ *     gq[i, k] = ((a_0 + a_1) + a_2) + a_3 over the waves that saw a source (wave w does when N > 64 w).
+ *   gp[j, k], gv[j, c]: one thread per source walks ALL queries of its cloud in increasing i: A[k] = fmaf(f, e_k, A[k]) and
+ *     V[c] = fmaf(P, g_i[c], V[c]) from +0. gv[j, c] = V[c]; gp[j, k] = A[k], and with v == NULL (the values are the points)
+ *     gp[j, k] = A[k] + V[k], one rounded addition. A gather: no atomics anywhere, one order of summation.
+ * Consequences: gq, gp, gv of a cloud depend on (q[s], p[s], v[s], out[s], m[s], l[s], g[s], C, scale) alone: bitwise the same
+ * for every batch, launch split, position in the batch and run; a channel's gv does not depend on the other channels or
+ * the rung; v == NULL gives gp bitwise equal to gp + gv (one float32 addition) of a copy of p passed as v.
+ * A NULL gq means "not wanted" and its kernel is not launched; likewise NULL gp and gv. gv must be NULL exactly when v is;
+ * with v given, gp may be NULL alone, gv may not (one kernel forms both).
+ * Errors, in this order, before any device work: those of nova_pointset_kernel_interpolate (out is an input here); then, with
+ * S > 0, NOVA_ERR_ARG for a null m, l (both entries) or g, for gv non-null with v == NULL, for gv == NULL with v and gp
+ * given, and for gq, gp and gv all NULL. S <= 0 returns 0 after the checks that do not look at pointers.
+ * Added without a version bump (the number is pinned by the tests of three earlier entries; a library without the new symbols
+ * fails to bind, loudly). */
+int nova_pointset_kernel_interpolate_stats(const float* q, const float* p, const float* v, float* out, float* m, float* l,
+                                           int S, int T, int N, int C, float scale, void* stream);
+int nova_pointset_kernel_interpolate_bwd(const float* q, const float* p, const float* v, const float* out, const float* m,
+                                         const float* l, const float* g, float* gq, float* gp, float* gv,
+                                         int S, int T, int N, int C, float scale, void* stream);
 
 /* Nearest match with indices, and its backward: the primitive under the Chamfer-type training losses of the reference,
  * robust_chamfer_distance on distChamfer (train_newloss.py:316-349) and the edge-consistency term (train_newloss.py:449-457:

@@ -507,6 +507,17 @@ int nova_pointset_kernel_interpolate(const float* q, const float* p, const float
   return pointset_kernel_interpolate(q, p, v, out, S, T, N, C, scale, (hipStream_t)stream);
 }
 
+int nova_pointset_kernel_interpolate_stats(const float* q, const float* p, const float* v, float* out, float* m, float* l, int S, int T,
+                                           int N, int C, float scale, void* stream) {
+  return pointset_kernel_interpolate_stats(q, p, v, out, m, l, S, T, N, C, scale, (hipStream_t)stream);
+}
+
+int nova_pointset_kernel_interpolate_bwd(const float* q, const float* p, const float* v, const float* out, const float* m, const float* l,
+                                         const float* g, float* gq, float* gp, float* gv, int S, int T, int N, int C, float scale,
+                                         void* stream) {
+  return pointset_kernel_interpolate_bwd(q, p, v, out, m, l, g, gq, gp, gv, S, T, N, C, scale, (hipStream_t)stream);
+}
+
 long long nova_pointset_assignment_state_bytes(int n) { return (long long)pointset_assignment_state_bytes(n); }
 
 int nova_pointset_assignment(const float* x, const float* y, int* col_of_row, float* cost, void* state, int B, int n, float clamp_lo,

@@ -40,15 +40,10 @@
 // slots, of which the square root is 20. At 32 lanes per SIMD and cycle, 1024 SIMDs and 2.4 GHz that is ~1.7e12 pairs/s
 // at C' = 3 and ~1.5e12 at C' = 8. The rescale costs 8 + 2 C' more whenever any of a wave's 64 lanes meets a new
 // minimum: about ln(N / 4) times per lane over a cloud in random order, so a few hundred of a wave's N / 4 sources.
-#include <float.h>
-
-#include "nova_internal.h"
-#include "pointset_common.h"
+#include "interp_common.h"
 
 namespace nova {
 
-constexpr int INTERP_MAX_N = NOVA_INTERP_MAX_POINTS;  // include/nova_hip.h
-constexpr int INTERP_MAX_C = NOVA_INTERP_MAX_CHANNELS;
 constexpr int INTERP_T = 256;      // threads per workgroup
 constexpr int INTERP_Q = 64;       // queries per workgroup: one per lane, in every wave
 constexpr int INTERP_WAVES = INTERP_T / INTERP_Q;
@@ -56,27 +51,6 @@ constexpr int INTERP_TILE = 1024;  // source points staged per LDS tile
 constexpr int INTERP_CHUNK = 64;   // consecutive sources one wave takes in turn
 constexpr int INTERP_GROUP = 4;    // sources whose reads and distances are issued together
 static_assert(INTERP_TILE % (INTERP_WAVES * INTERP_CHUNK) == 0, "chunk ownership is chunk mod 4 across tiles");
-
-__device__ __forceinline__ float interp_dist(float x0, float x1, float x2, float y0, float y1, float y2) {
-  return sqrtf(sqdist3(x0, x1, x2, y0, y1, y2));  // correctly rounded (v_sqrt_f32 and two correction steps), as pairwise_dist
-}
-// exp2((a - b) * scale): a - b <= 0 wherever it is used, so the result is in [0, 1]
-__device__ __forceinline__ float interp_weight(float a, float b, float scale) { return __builtin_amdgcn_exp2f(__fmul_rn(a - b, scale)); }
-
-// the values of tile source j: the point itself (CH == 3, from the float4 already read) or CH / 4 float4 of the value tile
-template <int CH> __device__ __forceinline__ void interp_values(float (&val)[CH], const f4v& s, const f4v* vs, int j) {
-  if (CH == 3) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) val[k] = s[k];
-  } else {
-#pragma unroll
-    for (int h = 0; h < CH / 4; ++h) {
-      const f4v u = vs[j * (CH / 4) + h];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) val[4 * h + k] = u[k];
-    }
-  }
-}
 
 // one source at distance d with the values val enters the running state (m, l, a) of a query
 template <int CH> __device__ __forceinline__ void interp_step(float& m, float& l, float (&a)[CH], float d, const float (&val)[CH], float scale) {
@@ -97,10 +71,12 @@ template <int CH> __device__ __forceinline__ void interp_step(float& m, float& l
 }
 
 // CH: numerators kept per query (3: v == NULL, the values are the source points; 4 | 8: explicit values of C <= CH channels)
-template <int CH>
+// STATS: also store the merged minimum M and weight sum L of every query, what the backward (interp_bwd.hip) starts from;
+// the scan and the merge are the same code, so out is the same bits with and without
+template <int CH, bool STATS>
 __global__ __launch_bounds__(INTERP_T) void interp_kernel(const float* __restrict__ q, const float* __restrict__ p,
-                                                          const float* __restrict__ v, float* __restrict__ out, int T, int N, int C,
-                                                          float scale, int qblocks) {
+                                                          const float* __restrict__ v, float* __restrict__ out, float* __restrict__ mo,
+                                                          float* __restrict__ lo, int T, int N, int C, float scale, int qblocks) {
   constexpr bool SELF = CH == 3;
   constexpr int VQ = SELF ? 0 : CH / 4;  // float4 of values per source
   constexpr int PART = 2 + CH;           // floats one wave hands over per query
@@ -209,33 +185,42 @@ __global__ __launch_bounds__(INTERP_T) void interp_kernel(const float* __restric
 #pragma unroll
     for (int k = 0; k < CH; ++k)
       if (k < C) o[k] = __fdiv_rn(a[k], l);  // l >= 1: the nearest source of the whole cloud has weight exactly 1
+    if (STATS) {
+      mo[c * (size_t)T + i] = M;
+      lo[c * (size_t)T + i] = l;
+    }
   }
 }
 
-template <int CH>
-static int interp_launch(const float* q, const float* p, const float* v, float* out, int S, int T, int N, int C, float scale, hipStream_t st) {
+template <int CH, bool STATS>
+static int interp_launch(const char* who, const float* q, const float* p, const float* v, float* out, float* m, float* l, int S, int T, int N,
+                         int C, float scale, hipStream_t st) {
   const int qblocks = (T + INTERP_Q - 1) / INTERP_Q;
   const long long blocks = (long long)S * qblocks;
-  if (blocks > 0x7fffffffLL) return set_error(NOVA_ERR_SHAPE, "pointset_kernel_interpolate: %d clouds of %d queries exceed one launch", S, T);
-  hipLaunchKernelGGL((interp_kernel<CH>), dim3((unsigned)blocks), dim3(INTERP_T), 0, st, q, p, v, out, T, N, C, scale, qblocks);
-  return check_launch("pointset_kernel_interpolate");
+  if (blocks > 0x7fffffffLL) return set_error(NOVA_ERR_SHAPE, "%s: %d clouds of %d queries exceed one launch", who, S, T);
+  hipLaunchKernelGGL((interp_kernel<CH, STATS>), dim3((unsigned)blocks), dim3(INTERP_T), 0, st, q, p, v, out, m, l, T, N, C, scale, qblocks);
+  return check_launch(who);
 }
 
 int pointset_kernel_interpolate(const float* q, const float* p, const float* v, float* out, int S, int T, int N, int C, float scale,
                                 hipStream_t st) {
-  if (T < 1 || T > INTERP_MAX_N || N < 1 || N > INTERP_MAX_N)
-    return set_error(NOVA_ERR_SHAPE, "pointset_kernel_interpolate: T %d or N %d outside 1 .. %d (NOVA_INTERP_MAX_POINTS)", T, N, INTERP_MAX_N);
-  if (C < 1 || C > INTERP_MAX_C)
-    return set_error(NOVA_ERR_SHAPE, "pointset_kernel_interpolate: C %d outside 1 .. %d (NOVA_INTERP_MAX_CHANNELS)", C, INTERP_MAX_C);
-  if (!v && C != 3)
-    return set_error(NOVA_ERR_ARG, "pointset_kernel_interpolate: v == NULL means the values are the source points and needs C == 3, got C %d", C);
-  if (!(scale >= 0.0f && scale <= FLT_MAX))
-    return set_error(NOVA_ERR_ARG, "pointset_kernel_interpolate: scale %g must be finite and >= 0 (log2(e) / temperature)", (double)scale);
-  if (S > 0 && (!q || !p || !out)) return set_error(NOVA_ERR_ARG, "pointset_kernel_interpolate: null pointer");
+  const char* who = "pointset_kernel_interpolate";
+  if (const int rc = interp_check(who, q, p, v, out, S, T, N, C, scale)) return rc;
   if (S <= 0) return 0;
-  if (!v) return interp_launch<3>(q, p, v, out, S, T, N, C, scale, st);
-  if (C <= 4) return interp_launch<4>(q, p, v, out, S, T, N, C, scale, st);
-  return interp_launch<8>(q, p, v, out, S, T, N, C, scale, st);
+  if (!v) return interp_launch<3, false>(who, q, p, v, out, nullptr, nullptr, S, T, N, C, scale, st);
+  if (C <= 4) return interp_launch<4, false>(who, q, p, v, out, nullptr, nullptr, S, T, N, C, scale, st);
+  return interp_launch<8, false>(who, q, p, v, out, nullptr, nullptr, S, T, N, C, scale, st);
+}
+
+int pointset_kernel_interpolate_stats(const float* q, const float* p, const float* v, float* out, float* m, float* l, int S, int T, int N,
+                                      int C, float scale, hipStream_t st) {
+  const char* who = "pointset_kernel_interpolate_stats";
+  if (const int rc = interp_check(who, q, p, v, out, S, T, N, C, scale)) return rc;
+  if (S > 0 && (!m || !l)) return set_error(NOVA_ERR_ARG, "%s: null pointer (m or l)", who);
+  if (S <= 0) return 0;
+  if (!v) return interp_launch<3, true>(who, q, p, v, out, m, l, S, T, N, C, scale, st);
+  if (C <= 4) return interp_launch<4, true>(who, q, p, v, out, m, l, S, T, N, C, scale, st);
+  return interp_launch<8, true>(who, q, p, v, out, m, l, S, T, N, C, scale, st);
 }
 
 }  // namespace nova

@@ -218,6 +218,11 @@ int pointset_knn(const float* x, const float* y, int* idx, float* d2, int S, int
 // ---- interp.hip (distance-weighted interpolation of values over a cloud set; point counts 1 .. NOVA_INTERP_MAX_POINTS, 1 .. NOVA_INTERP_MAX_CHANNELS channels)
 int pointset_kernel_interpolate(const float* q, const float* p, const float* v, float* out, int S, int T, int N, int C, float scale,
                                 hipStream_t st);
+int pointset_kernel_interpolate_stats(const float* q, const float* p, const float* v, float* out, float* m, float* l, int S, int T, int N,
+                                      int C, float scale, hipStream_t st);
+// ---- interp_bwd.hip (its backward: gradients of the queries, the source points and the values, no [T, N] array, no atomics)
+int pointset_kernel_interpolate_bwd(const float* q, const float* p, const float* v, const float* out, const float* m, const float* l,
+                                    const float* g, float* gq, float* gp, float* gv, int S, int T, int N, int C, float scale, hipStream_t st);
 // ---- assign.hip (optimal assignment of two clouds by a batched integer auction; point counts 1 .. NOVA_ASSIGN_MAX_POINTS)
 size_t pointset_assignment_state_bytes(int n);
 int pointset_assignment(const float* x, const float* y, int* col, float* cost, void* state, int B, int n, float lo, float hi,

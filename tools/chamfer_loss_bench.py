@@ -22,7 +22,7 @@ import os
 import subprocess
 import sys
 
-from pointset_bench_common import shell_clouds
+from pointset_bench_common import best_and_spread, calls_per_window, shell_clouds, window
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = {"32x2048": (32, 2048), "1x15000": (1, 15000)}
@@ -46,29 +46,6 @@ def step(loss_fn, pred, target):
     loss = loss_fn(pred, target)
     loss.backward()
     return loss.detach(), pred.grad
-
-
-def window(fn, inner):
-    """(result, seconds per call) of `inner` calls in a row between two device events."""
-    import torch
-
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    a.record()
-    for _ in range(inner):
-        out = fn()
-    b.record()
-    torch.cuda.synchronize()
-    return out, a.elapsed_time(b) / 1e3 / inner
-
-
-def calls_per_window(fn, seconds):
-    """How many calls in a row last about `seconds` (from one warm call)."""
-    return max(1, int(seconds / max(window(fn, 1)[1], 1e-6)) + 1)
-
-
-def best_and_spread(times):
-    return min(times), (max(times) - min(times)) / min(times)
 
 
 def run_case(name, reps, hip_only, seconds):

@@ -1,5 +1,5 @@
 """Seeded inputs and device-event timers shared by the point-set bench tools (chamfer_matrix_bench, emd_matrix_bench,
-fps_bench, assignment_bench, knn_bench, interp_bench). torch is imported on first use: knn_bench's and interp_bench's parent
+fps_bench, assignment_bench, knn_bench, interp_bench, chamfer_loss_bench, interp_grad_bench). torch is imported on first use: knn_bench's and interp_bench's parent
 processes do no GPU work."""
 
 
@@ -49,3 +49,26 @@ def timed(fn, reps):
         torch.cuda.synchronize()
         times.append(a.elapsed_time(b) / 1e3)
     return out, min(times), (max(times) - min(times)) / min(times)
+
+
+def window(fn, inner):
+    """(result, seconds per call) of `inner` calls in a row between two device events."""
+    import torch
+
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    a.record()
+    for _ in range(inner):
+        out = fn()
+    b.record()
+    torch.cuda.synchronize()
+    return out, a.elapsed_time(b) / 1e3 / inner
+
+
+def calls_per_window(fn, seconds):
+    """How many calls in a row last about `seconds` (from one warm call)."""
+    return max(1, int(seconds / max(window(fn, 1)[1], 1e-6)) + 1)
+
+
+def best_and_spread(times):
+    return min(times), (max(times) - min(times)) / min(times)
