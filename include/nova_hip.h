@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NOVA_HIP_VERSION 405 /* still 0.4.5 (tests/test_pointset_fps.py pins the number; a library without the new symbols fails to bind, loudly): nova_pointset_kernel_interpolate_stats, nova_pointset_kernel_interpolate_bwd (the interpolation forward with its statistics and its backward, for nova_pointcloud_amd.sampling); nova_pointset_nearest_match, nova_pointset_nearest_match_bwd (nearest match with indices and its backward, for the Chamfer-type training losses); nova_pointset_knn (exact k nearest neighbours of a cloud set); nova_pointset_assignment, nova_pointset_assignment_state_bytes, nova_pointset_assignment_rounds (optimal assignment of two clouds by a batched integer auction: the exact EMD on the GPU); 0.4.5: nova_pointset_farthest_point_sample (farthest point sampling of a cloud set, to bring sets to a common point count); 0.4.4: nova_pointset_occupancy_grid (occupancy grid of a cloud set for the JSD metric); 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
+#define NOVA_HIP_VERSION 405 /* still 0.4.5 (tests/test_pointset_fps.py pins the number; a library without the new symbols fails to bind, loudly): nova_pointset_matched_dist, nova_pointset_matched_dist_bwd (the distance of matched pairs under a given permutation and its backward, for the exact-assignment EMD training loss); nova_pointset_kernel_interpolate_stats, nova_pointset_kernel_interpolate_bwd (the interpolation forward with its statistics and its backward, for nova_pointcloud_amd.sampling); nova_pointset_nearest_match, nova_pointset_nearest_match_bwd (nearest match with indices and its backward, for the Chamfer-type training losses); nova_pointset_knn (exact k nearest neighbours of a cloud set); nova_pointset_assignment, nova_pointset_assignment_state_bytes, nova_pointset_assignment_rounds (optimal assignment of two clouds by a batched integer auction: the exact EMD on the GPU); 0.4.5: nova_pointset_farthest_point_sample (farthest point sampling of a cloud set, to bring sets to a common point count); 0.4.4: nova_pointset_occupancy_grid (occupancy grid of a cloud set for the JSD metric); 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
 
 typedef enum { NOVA_F32 = 0, NOVA_BF16 = 1, NOVA_F16 = 2 } nova_dtype;
 typedef enum { NOVA_ACT_NONE = 0, NOVA_ACT_GELU_ERF = 1, NOVA_ACT_SILU = 2 } nova_act;
@@ -496,6 +496,43 @@ int nova_pointset_nearest_match(const float* x, const float* y, float* d, int* i
                                 float clamp_hi, int unit_norm, void* stream);
 int nova_pointset_nearest_match_bwd(const float* x, const float* y, const int* idx, const float* g, float* gx, float* gy, int B,
                                     int N, int M, float clamp_lo, float clamp_hi, int unit_norm, void* stream);
+
+/* Distance of matched pairs under a GIVEN permutation, and its backward: the primitive under the exact-assignment EMD
+ * training loss. The reference's emd_approx (train_newloss.py:352-377) is the mean matched distance under the optimal
+ * assignment of the clamped clouds, cost floored at 1e-8, and its EMD term (train_newloss.py:418-424) goes through numpy
+ * and carries no gradient. The optimal permutation is piecewise constant in the points, so with the assignment held fixed
+ * (nova_pointset_assignment, or scipy on the host) the loss is a sum of n distances between matched pairs, and the gradient
+ * of that sum is the gradient of the EMD almost everywhere. Nothing of size n^2 exists in either pass.
+ * Inputs.  x, y [B, n, 3] float32, finite. idx int32 [B, n]: the column matched to row i. inv int32 [B, n]: the row matched
+ *   to column j, i.e. the inverse permutation (inv[b, idx[b, i]] = i); the backward takes it from the caller.
+ * Clamp.  c(v) = fminf(fmaxf(v, clamp_lo), clamp_hi) per coordinate; pass -inf and +inf for no clamp.
+ * nova_pointset_matched_dist: with a = idx[b, i] and e = c(x[b, i]) - c(y[b, a]) per axis (float32 subtractions),
+ *     d2 = fmaf(e2, e2, fmaf(e1, e1, e0 * e0))          the product rounded once, the two fused multiply-adds once each
+ *     d[b, i] = fmaxf(sqrtf(d2), floor)                 the square root correctly rounded
+ *   Before the floor, sqrtf(d2) is bit for bit the entry D[b, i, a] of nova_pointset_pairwise_dist and the cost c(i, a) of
+ *   nova_pointset_assignment under the same clamp. An idx outside 0 .. n-1 is never dereferenced and gives d[b, i] = NaN.
+ * nova_pointset_matched_dist_bwd: from g[b, i] = dL/dd[b, i] (float32 [B, n]), gx and gy [B, n, 3] (float32). For the pair
+ *   (i, a), with e as above and dist = sqrtf(d2) recomputed:
+ *     t_k = (g_i * e_k) / dist per axis, the product rounded, then one IEEE division
+ *     t = 0 exactly when dist == 0 or dist < floor (torch.clamp_min's backward: no gradient below the floor, gradient at it;
+ *     and the subgradient convention of nova_pointset_nearest_match_bwd: coincident points give no gradient and no NaN)
+ *   then r_k = 0 for every coordinate of the DIFFERENTIATED point that lies outside [clamp_lo, clamp_hi], bounds inclusive
+ *   (torch.clamp's backward), r_k = t_k otherwise:
+ *     gx[b, i] = r(t)    from the pair (i, idx[b, i]),  masked at x[b, i]
+ *     gy[b, j] = r(-t)   from the pair (inv[b, j], j),  masked at y[b, j]; t is recomputed by the thread that owns j
+ *   Both outputs are gathers, one thread per output row: no scatter writes and no atomics, and every output element is
+ *   written exactly once, even for a corrupt index. An idx (for gx) or inv (for gy) outside 0 .. n-1 is never dereferenced
+ *   and gives a zero row. gy does not consult idx: for an inv that is not the inverse of idx, gy is the gradient under inv.
+ * Consequences: d, gx and gy of a cloud depend on (x[b], y[b], idx[b], inv[b], g[b], the clamp, floor) alone: bitwise the
+ * same for every batch, launch split, position in the batch and run.
+ * NOVA_ERR_ARG for a null pointer, for clamp_lo > clamp_hi (or either NaN) and for floor negative or NaN; NOVA_ERR_SHAPE for
+ * B > 65535. B <= 0 or n <= 0 is a no-op returning 0 (after the clamp and floor checks, as in nova_pointset_nearest_match).
+ * Everything is checked before any device work. Added without a version bump (a library without the new symbols fails to
+ * bind, loudly). */
+int nova_pointset_matched_dist(const float* x, const float* y, const int* idx, float* d, int B, int n, float clamp_lo,
+                               float clamp_hi, float floor, void* stream);
+int nova_pointset_matched_dist_bwd(const float* x, const float* y, const int* idx, const int* inv, const float* g, float* gx,
+                                   float* gy, int B, int n, float clamp_lo, float clamp_hi, float floor, void* stream);
 
 /* Optimal assignment between x [B, n, 3] and y [B, n, 3] (float32, finite), pair by pair: the permutation that minimises
  * the mean matched distance, i.e. the earth mover's distance that compute_emd_distance (test_optimize.py:385-415) and

@@ -472,6 +472,22 @@ int nova_pointset_nearest_match_bwd(const float* x, const float* y, const int* i
   return pointset_nearest_match_bwd(x, y, idx, g, gx, gy, B, N, M, clamp_lo, clamp_hi, unit_norm, (hipStream_t)stream);
 }
 
+int nova_pointset_matched_dist(const float* x, const float* y, const int* idx, float* d, int B, int n, float clamp_lo, float clamp_hi,
+                               float floor, void* stream) {
+  NOVA_REQUIRE(B <= 0 || n <= 0 || (x && y && idx && d), NOVA_ERR_ARG, "pointset_matched_dist: null pointer");
+  NOVA_REQUIRE(clamp_lo <= clamp_hi, NOVA_ERR_ARG, "pointset_matched_dist: empty clamp range");
+  NOVA_REQUIRE(floor >= 0.f, NOVA_ERR_ARG, "pointset_matched_dist: floor must be >= 0");
+  return pointset_matched_dist(x, y, idx, d, B, n, clamp_lo, clamp_hi, floor, (hipStream_t)stream);
+}
+
+int nova_pointset_matched_dist_bwd(const float* x, const float* y, const int* idx, const int* inv, const float* g, float* gx, float* gy,
+                                   int B, int n, float clamp_lo, float clamp_hi, float floor, void* stream) {
+  NOVA_REQUIRE(B <= 0 || n <= 0 || (x && y && idx && inv && g && gx && gy), NOVA_ERR_ARG, "pointset_matched_dist_bwd: null pointer");
+  NOVA_REQUIRE(clamp_lo <= clamp_hi, NOVA_ERR_ARG, "pointset_matched_dist_bwd: empty clamp range");
+  NOVA_REQUIRE(floor >= 0.f, NOVA_ERR_ARG, "pointset_matched_dist_bwd: floor must be >= 0");
+  return pointset_matched_dist_bwd(x, y, idx, inv, g, gx, gy, B, n, clamp_lo, clamp_hi, floor, (hipStream_t)stream);
+}
+
 int nova_pointset_chamfer_matrix(const float* x, const float* y, float* cd, int A, int B, int N, int M, int ldc, int symmetric,
                                  void* stream) {
   NOVA_REQUIRE(A <= 0 || B <= 0 || (x && y && cd), NOVA_ERR_ARG, "pointset_chamfer_matrix: null pointer");

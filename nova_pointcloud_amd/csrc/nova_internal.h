@@ -203,6 +203,11 @@ int pointset_nearest_match(const float* x, const float* y, float* d, int* idx, i
                            hipStream_t st);
 int pointset_nearest_match_bwd(const float* x, const float* y, const int* idx, const float* g, float* gx, float* gy, int B, int N, int M,
                                float lo, float hi, int unit, hipStream_t st);
+// ---- matched.hip (distance of matched pairs under a given permutation and its backward: the exact-assignment EMD training loss)
+int pointset_matched_dist(const float* x, const float* y, const int* idx, float* d, int B, int n, float lo, float hi, float floor,
+                          hipStream_t st);
+int pointset_matched_dist_bwd(const float* x, const float* y, const int* idx, const int* inv, const float* g, float* gx, float* gy, int B,
+                              int n, float lo, float hi, float floor, hipStream_t st);
 // ---- chamfer.hip (all-pairs Chamfer matrix for MMD / COV / 1-NNA)
 int pointset_chamfer_matrix(const float* x, const float* y, float* cd, int A, int B, int N, int M, int ldc, int symmetric,
                             hipStream_t st);

@@ -90,6 +90,8 @@ SIGNATURES = {
     "nova_pointset_pairwise_dist": [c_void_p] * 3 + [c_int] * 3 + [c_float, c_float, c_void_p],
     "nova_pointset_nearest_match": [c_void_p] * 4 + [c_int] * 3 + [c_float, c_float, c_int, c_void_p],
     "nova_pointset_nearest_match_bwd": [c_void_p] * 6 + [c_int] * 3 + [c_float, c_float, c_int, c_void_p],
+    "nova_pointset_matched_dist": [c_void_p] * 4 + [c_int] * 2 + [c_float] * 3 + [c_void_p],
+    "nova_pointset_matched_dist_bwd": [c_void_p] * 7 + [c_int] * 2 + [c_float] * 3 + [c_void_p],
     "nova_pointset_chamfer_matrix": [c_void_p] * 3 + [c_int] * 6 + [c_void_p],
     "nova_pointset_emd_matrix": [c_void_p] * 3 + [c_int] * 4 + [c_void_p],
     "nova_pointset_occupancy_grid": [c_void_p] * 5 + [c_int] * 5 + [c_void_p],
