@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define NOVA_HIP_VERSION 405 /* still 0.4.5 (tests/test_pointset_fps.py pins the number; a library without the new symbols fails to bind, loudly): nova_pointset_matched_dist, nova_pointset_matched_dist_bwd (the distance of matched pairs under a given permutation and its backward, for the exact-assignment EMD training loss); nova_pointset_kernel_interpolate_stats, nova_pointset_kernel_interpolate_bwd (the interpolation forward with its statistics and its backward, for nova_pointcloud_amd.sampling); nova_pointset_nearest_match, nova_pointset_nearest_match_bwd (nearest match with indices and its backward, for the Chamfer-type training losses); nova_pointset_knn (exact k nearest neighbours of a cloud set); nova_pointset_assignment, nova_pointset_assignment_state_bytes, nova_pointset_assignment_rounds (optimal assignment of two clouds by a batched integer auction: the exact EMD on the GPU); 0.4.5: nova_pointset_farthest_point_sample (farthest point sampling of a cloud set, to bring sets to a common point count); 0.4.4: nova_pointset_occupancy_grid (occupancy grid of a cloud set for the JSD metric); 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
+#define NOVA_HIP_VERSION 405 /* still 0.4.5 (tests/test_pointset_fps.py pins the number; a library without the new symbols fails to bind, loudly): nova_pointset_neighbor_aggregate, nova_pointset_neighbor_inverse, nova_pointset_neighbor_aggregate_bwd (kNN neighbourhood feature aggregation, its inverse neighbour list and its backward, for nova_pointcloud_amd.neighbors); nova_pointset_matched_dist, nova_pointset_matched_dist_bwd (the distance of matched pairs under a given permutation and its backward, for the exact-assignment EMD training loss); nova_pointset_kernel_interpolate_stats, nova_pointset_kernel_interpolate_bwd (the interpolation forward with its statistics and its backward, for nova_pointcloud_amd.sampling); nova_pointset_nearest_match, nova_pointset_nearest_match_bwd (nearest match with indices and its backward, for the Chamfer-type training losses); nova_pointset_knn (exact k nearest neighbours of a cloud set); nova_pointset_assignment, nova_pointset_assignment_state_bytes, nova_pointset_assignment_rounds (optimal assignment of two clouds by a batched integer auction: the exact EMD on the GPU); 0.4.5: nova_pointset_farthest_point_sample (farthest point sampling of a cloud set, to bring sets to a common point count); 0.4.4: nova_pointset_occupancy_grid (occupancy grid of a cloud set for the JSD metric); 0.4.3: nova_pointset_emd_matrix (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA); 0.4.2: nova_pointset_chamfer_matrix (all-pairs Chamfer matrix for MMD / COV / 1-NNA); 0.4.1: nova_decoder_denoise_echo (guidance renorm with any sampler step); 0.4.0 (round 4): the loader checks this number against its own; nova_attn_fwd_lse / nova_attn_bwd carry a key_limit pointer before the stream, nova_row_norm_bwd, nova_act_fwd, nova_act_bwd, nova_debug_drop_graphs (all added after 0.3.0 without a bump), nova_prof slots 7-9; 0.3.0: NOVA_F16 storage mode through every dtype-taking entry, nova_row_norm_chain takes a dtype, nova_debug_set_attn_variant; 0.2.2: nova_attn_fwd_lse, nova_attn_bwd; 0.2.1: nova_adaln_fc1, nova_row_norm_chain (0.2.0: 3-pass guidance fields in nova_sampler_step, KV-cached block stack, nova_modulate_rows) */
 
 typedef enum { NOVA_F32 = 0, NOVA_BF16 = 1, NOVA_F16 = 2 } nova_dtype;
 typedef enum { NOVA_ACT_NONE = 0, NOVA_ACT_GELU_ERF = 1, NOVA_ACT_SILU = 2 } nova_act;
@@ -371,6 +371,66 @@ int nova_pointset_farthest_point_sample(const float* x, const int* start, int* i
 #define NOVA_KNN_MAX_K 32
 #define NOVA_KNN_MAX_POINTS 65536
 int nova_pointset_knn(const float* x, const float* y, int* idx, float* d2, int S, int N, int M, int k, int exclude_self, void* stream);
+
+/* kNN neighbourhood feature aggregation, forward and backward: for every query row of idx [S, N, k] (int32, as
+ * nova_pointset_knn writes it) the mean, or the weighted sum, of the k rows of the features f [S, M, C] (float32) it names,
+ * cloud by cloud. It is the reference's EdgeAligner.extract_edge_features,
+ * diffnext/models/transformers/transformer_pointcloud_nova.py:176-190 (torch.cdist(points, points), topk(min(8, N)), a
+ * gather of the neighbours' features to [B, N, k, C], their mean over k, features - mean), called for every subset in
+ * EdgeAligner.forward (:192-223) and from AutoregressiveDiffusion.forward (:286-290) on 768-wide features, where PyTorch
+ * keeps the [B, N, N] matrix and the [B, N, k, C] tensor alive for the backward. Here the indices come from
+ * nova_pointset_knn and neither pass stores anything of size N M or N k C. The subtraction from the centre feature is the
+ * caller's (one torch op).
+ * DEVIATION, on purpose: the gather expression at :184-187 does not run as written for [B, N, C] features (expand(-1, k, -1)
+ * is applied to a 4-D tensor). The definition is that function's comment: the mean of the k nearest neighbours' features.
+ * Every operation below is rounded once to float32 and nothing is fused; w [S, N, k] (float32) is optional.
+ * nova_pointset_neighbor_aggregate: for query i of cloud s and channel c, with j_t = idx[s, i, t] and
+ *     term_t = f[s, j_t, c]                  (w == NULL, the mean form)
+ *     term_t = w[s, i, t] * f[s, j_t, c]     (weighted form: one rounded product)
+ *     term_t = +0.0f                         for j_t outside 0 .. M-1, in both forms: such an index is never dereferenced
+ *   acc = term_0, then acc = acc + term_t for t = 1 .. k-1 in that order (k - 1 rounded additions, none for k = 1);
+ *   out[s, i, c] = acc / (float)k (one correctly rounded division; an out-of-range index still counts in the divisor) in
+ *   the mean form, out[s, i, c] = acc in the weighted form. Duplicate indices inside a row are allowed.
+ * nova_pointset_neighbor_inverse: the inverse neighbour list that makes the feature gradient a gather. An edge is a pair
+ *   (i, t) with the id e = i k + t; it is in range when 0 <= idx[s, i, t] < M. offsets [S, M + 1] (int32):
+ *   offsets[s, j] = the number of in-range edges naming a target below j, so offsets[s, 0] = 0 and offsets[s, M] = their
+ *   total. edges [S, N k] (int32): edges[s, offsets[s, j] .. offsets[s, j + 1] - 1] = the ids of the edges naming j, in
+ *   increasing order: the stable sort of the in-range edges by target. Slots past offsets[s, M] are not written. Built by
+ *   two scans (one thread per target and quarter of the edge range walks the indices of its cloud and counts; a per-cloud
+ *   prefix sum; the same walk again writing ids in the order met, each quarter starting behind the recounted matches of the
+ *   quarters before it): 3 M N k integer compares per cloud, integers only, no atomics, no sort.
+ * nova_pointset_neighbor_aggregate_bwd: from g [S, N, C] = dLoss/dout, gf [S, M, C] and gw [S, N, k] (float32).
+ *   gf[s, j, c]: with e_0 < e_1 < ... the edges of j's segment of the list, i_r = e_r / k (integer division) and
+ *       term_r = w[s, e_r] * g[s, i_r, c]     (weighted form, w flat over (i, t): one rounded product)
+ *       term_r = g[s, i_r, c] / (float)k      (mean form: the forward's division, correctly rounded, not a product with 1/k)
+ *     acc = term_0, then acc = acc + term_r in increasing r: accumulated from the first edge's term, not from 0 plus that
+ *     term. A target no edge names gets exactly +0.0f, written by the kernel. One wave per target walks the segment: a
+ *     gather, no atomics, one order. An edge id outside 0 .. N k - 1 in a list that is not this idx's inverse is never
+ *     dereferenced (its term is +0.0f) and a segment is cut to 0 .. N k; gf is then the gradient under that list.
+ *   gw[s, i, t] = sum_c g[s, i, c] * f[s, j_t, c], and +0.0f for j_t outside 0 .. M-1, in one reduction shape for every C
+ *     and every launch: lane l of 64 forms p_l = +0.0f for l >= C, else the rounded product at c = l, then
+ *     p_l = p_l + (the rounded product at c) for c = l + 64, l + 128, ... < C in that order; the 64 p_l are then summed by
+ *     six pairwise steps in which both partners take a + b: lanes i <-> 7 - i inside each group of 8, then xor 1, xor 2,
+ *     i <-> 15 - i inside each row of 16, rows 0|1 and 2|3 of 16 lanes, the two halves of 32.
+ *   gf == NULL or gw == NULL means "not wanted" and its kernel is not launched; offsets and edges are read only for gf.
+ * Consequences: out, offsets, edges, gf and gw of a cloud depend on that cloud's inputs, k and C alone: bitwise the same for
+ * every batch, launch split, position in the batch and run; a channel of out or gf does not depend on the other channels.
+ * Limits: 1 <= k <= NOVA_KNN_MAX_K (a row's indices live one per lane); 1 <= N, M <= NOVA_KNN_MAX_POINTS (edge ids and
+ * offsets stay below 2^21); 1 <= C <= NOVA_NEIGHBOR_MAX_CHANNELS; at most 65535 clouds per call.
+ * Errors, in this order, before any device work, the same in all three entries (the inverse has no C):
+ *   NOVA_ERR_SHAPE for N or M outside their range; NOVA_ERR_SHAPE for C outside its range; NOVA_ERR_ARG for k outside its
+ *   range; NOVA_ERR_SHAPE for S > 65535. S <= 0 returns 0 after these. Then NOVA_ERR_ARG for a null f, idx or out
+ *   (aggregate), idx, offsets or edges (inverse), f, idx or g (bwd); bwd only: NOVA_ERR_ARG for gw given with w == NULL, for
+ *   gf and gw both NULL, for gf given with a null offsets or edges; last, NOVA_ERR_ARG when an output overlaps an input or
+ *   another output (outputs must not overlap inputs).
+ * Added without a version bump (the number is pinned by the tests of three earlier entries; a library without the new
+ * symbols fails to bind, loudly). */
+#define NOVA_NEIGHBOR_MAX_CHANNELS 4096
+int nova_pointset_neighbor_aggregate(const float* f, const int* idx, const float* w, float* out, int S, int N, int M, int k, int C,
+                                     void* stream);
+int nova_pointset_neighbor_inverse(const int* idx, int* offsets, int* edges, int S, int N, int M, int k, void* stream);
+int nova_pointset_neighbor_aggregate_bwd(const float* f, const int* idx, const float* w, const float* g, const int* offsets,
+                                         const int* edges, float* gf, float* gw, int S, int N, int M, int k, int C, void* stream);
 
 /* Distance-weighted interpolation: for every query point of q [S, T, 3] the average of the values v [S, N, C] of ALL source
  * points p [S, N, 3] of its cloud (float32, finite), weighted by softmax(-distance / temperature), without ever storing a

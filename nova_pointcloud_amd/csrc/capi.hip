@@ -518,6 +518,20 @@ int nova_pointset_knn(const float* x, const float* y, int* idx, float* d2, int S
   return pointset_knn(x, y, idx, d2, S, N, M, k, exclude_self, (hipStream_t)stream);
 }
 
+int nova_pointset_neighbor_aggregate(const float* f, const int* idx, const float* w, float* out, int S, int N, int M, int k, int C,
+                                     void* stream) {
+  return pointset_neighbor_aggregate(f, idx, w, out, S, N, M, k, C, (hipStream_t)stream);
+}
+
+int nova_pointset_neighbor_inverse(const int* idx, int* offsets, int* edges, int S, int N, int M, int k, void* stream) {
+  return pointset_neighbor_inverse(idx, offsets, edges, S, N, M, k, (hipStream_t)stream);
+}
+
+int nova_pointset_neighbor_aggregate_bwd(const float* f, const int* idx, const float* w, const float* g, const int* offsets,
+                                         const int* edges, float* gf, float* gw, int S, int N, int M, int k, int C, void* stream) {
+  return pointset_neighbor_aggregate_bwd(f, idx, w, g, offsets, edges, gf, gw, S, N, M, k, C, (hipStream_t)stream);
+}
+
 int nova_pointset_kernel_interpolate(const float* q, const float* p, const float* v, float* out, int S, int T, int N, int C, float scale,
                                      void* stream) {
   return pointset_kernel_interpolate(q, p, v, out, S, T, N, C, scale, (hipStream_t)stream);

@@ -220,6 +220,12 @@ int pointset_occupancy_grid(const float* x, long long* counters, long long* bern
 int pointset_farthest_point_sample(const float* x, const int* start, int* idx, float* dist, int S, int N, int n, hipStream_t st);
 // ---- knn.hip (exact k nearest neighbours of a cloud set; k 1 .. NOVA_KNN_MAX_K, point counts 1 .. NOVA_KNN_MAX_POINTS)
 int pointset_knn(const float* x, const float* y, int* idx, float* d2, int S, int N, int M, int k, int exclude_self, hipStream_t st);
+// ---- neighbor.hip (kNN neighbourhood feature aggregation, its inverse neighbour list and its backward; 1 .. NOVA_NEIGHBOR_MAX_CHANNELS channels)
+int pointset_neighbor_aggregate(const float* f, const int* idx, const float* w, float* out, int S, int N, int M, int k, int C,
+                                hipStream_t st);
+int pointset_neighbor_inverse(const int* idx, int* offsets, int* edges, int S, int N, int M, int k, hipStream_t st);
+int pointset_neighbor_aggregate_bwd(const float* f, const int* idx, const float* w, const float* g, const int* offsets,
+                                    const int* edges, float* gf, float* gw, int S, int N, int M, int k, int C, hipStream_t st);
 // ---- interp.hip (distance-weighted interpolation of values over a cloud set; point counts 1 .. NOVA_INTERP_MAX_POINTS, 1 .. NOVA_INTERP_MAX_CHANNELS channels)
 int pointset_kernel_interpolate(const float* q, const float* p, const float* v, float* out, int S, int T, int N, int C, float scale,
                                 hipStream_t st);

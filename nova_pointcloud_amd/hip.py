@@ -97,6 +97,9 @@ SIGNATURES = {
     "nova_pointset_occupancy_grid": [c_void_p] * 5 + [c_int] * 5 + [c_void_p],
     "nova_pointset_farthest_point_sample": [c_void_p] * 4 + [c_int] * 3 + [c_void_p],
     "nova_pointset_knn": [c_void_p] * 4 + [c_int] * 5 + [c_void_p],
+    "nova_pointset_neighbor_aggregate": [c_void_p] * 4 + [c_int] * 5 + [c_void_p],
+    "nova_pointset_neighbor_inverse": [c_void_p] * 3 + [c_int] * 4 + [c_void_p],
+    "nova_pointset_neighbor_aggregate_bwd": [c_void_p] * 8 + [c_int] * 5 + [c_void_p],
     "nova_pointset_kernel_interpolate": [c_void_p] * 4 + [c_int] * 4 + [c_float, c_void_p],
     "nova_pointset_kernel_interpolate_stats": [c_void_p] * 6 + [c_int] * 4 + [c_float, c_void_p],
     "nova_pointset_kernel_interpolate_bwd": [c_void_p] * 10 + [c_int] * 4 + [c_float, c_void_p],
