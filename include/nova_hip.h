@@ -772,7 +772,9 @@ typedef struct {
  * Workspaces in `dtype`: ws_u, ws_h, ws_f, ws_g [S*n, D]; ws_a [mod_steps*S*n, D]; ws_mod [mod_steps*S*n, (3*depth+2)*D].
  * mod_steps = 1: the AdaLN projection of SiLU(zc + temb[i]) (normalization.py:35) is computed inside every step;
  * mod_steps = steps: for all steps in ONE GEMM ahead of the loop (the condition rows do not change during the loop,
- * diffusion_mlp.py:93-95), which needs the steps-times larger ws_a / ws_mod. Same results either way. */
+ * diffusion_mlp.py:93-95), which needs the steps-times larger ws_a / ws_mod. Same results either way.
+ * The whole plan is checked before the first launch: a refused call (mod_steps, S, a step that needs more guidance passes
+ * than S / B, extra_kind, P > 64, renorm < 1 with a step that is not the Euler step) launches nothing and leaves x as it was. */
 int nova_decoder_denoise(const nova_decoder* dec, const void* zc, const void* temb, float* x, const nova_sampler_step* sched,
                          const float* noise, float renorm, float* echo_energy, int steps, int S, int B, int n, int P, int D,
                          void* ws_a, void* ws_u, void* ws_h, void* ws_f, void* ws_g, void* ws_mod, float* ws_v, int mod_steps,

@@ -581,6 +581,20 @@ static int decoder_denoise_launches(const nova_decoder* dec, const void* zc, con
   const long mod_ld = (long)(3 * depth + 2) * D;
   const size_t nP = (size_t)B * n * P;
   NOVA_REQUIRE(mod_steps == 1 || mod_steps == steps, NOVA_ERR_ARG, "decoder_denoise: mod_steps must be 1 or steps");
+  // The whole plan is checked before the first launch: a refused call leaves x (and the echo energy / rows) as they were, on the direct
+  // path as under capture. The loop below used to check step i after steps 0 .. i-1 had been launched.
+  NOVA_REQUIRE(P >= 1 && P <= 64, NOVA_ERR_SHAPE, "decoder_denoise: patch vector length %d unsupported", P);
+  for (int i = 0; i < steps; ++i) {
+    const nova_sampler_step& s = sched[i];
+    const int cfg = s.guidance > 1.0f ? 1 : 0;
+    NOVA_REQUIRE(s.extra_kind >= 0 && s.extra_kind <= 2, NOVA_ERR_ARG, "decoder_denoise: extra_kind must be 0, 1 or 2");
+    const int passes = cfg ? (s.extra_kind ? 3 : 2) : 1;
+    NOVA_REQUIRE(S >= passes * B, NOVA_ERR_SHAPE, "decoder_denoise: step %d needs %d guidance passes but S = %d, B = %d", i, passes, S, B);
+    // the scalar echo energy follows the Euler step only, on the steps without guidance (guidance_trunc) as well: they scale it too
+    NOVA_REQUIRE(!do_renorm || echo_rows || (s.kx == 0.f && s.kv == 1.f && s.cx == 1.f && s.sigma == 0.f && s.clip <= 0.f),
+                 NOVA_ERR_ARG, "decoder_denoise: guidance renorm with a scalar echo energy holds for the flow-matching Euler step only "
+                 "(other samplers: nova_decoder_denoise_echo with the echo rows)");
+  }
   // mod_steps == steps: the AdaLN projections of ALL steps in one GEMM ahead of the loop (M = steps * S * n rows: the large-M
   // kernel at ~2.5x the rate of the per-step small-M launches, and two launches fewer per step). Rows are laid out per
   // step for the full S sequences; a step that runs fewer guidance passes (guidance_trunc) reads its leading rows.
@@ -595,12 +609,7 @@ static int decoder_denoise_launches(const nova_decoder* dec, const void* zc, con
     const SamplerStep sp{sched[i].guidance, sched[i].kx,    sched[i].kv,          sched[i].clip,      sched[i].c0,
                          sched[i].cx,       sched[i].sigma, sched[i].extra_scale, sched[i].extra_kind};
     const int cfg = sp.guidance > 1.0f ? 1 : 0;
-    NOVA_REQUIRE(sp.extra_kind >= 0 && sp.extra_kind <= 2, NOVA_ERR_ARG, "decoder_denoise: extra_kind must be 0, 1 or 2");
     const int passes = cfg ? (sp.extra_kind ? 3 : 2) : 1;
-    NOVA_REQUIRE(S >= passes * B, NOVA_ERR_SHAPE, "decoder_denoise: step %d needs %d guidance passes but S = %d, B = %d", i, passes, S, B);
-    NOVA_REQUIRE(!(do_renorm && cfg) || echo_rows || (sp.kx == 0.f && sp.kv == 1.f && sp.cx == 1.f && sp.sigma == 0.f && sp.clip <= 0.f),
-                 NOVA_ERR_ARG, "decoder_denoise: guidance renorm with a scalar echo energy holds for the flow-matching Euler step only "
-                 "(other samplers: nova_decoder_denoise_echo with the echo rows)");
     const int Se = passes * B;
     const long rows = (long)Se * n;
     if (hoist) {
@@ -756,7 +765,11 @@ int nova_decoder_denoise(const nova_decoder* dec, const void* zc, const void* te
   }
   std::string key;
   key.reserve(512 + sizeof(nova_sampler_step) * steps + sizeof(nova_mlp_block) * dec->depth);
-  key_put(key, *dec);
+  // field by field: the struct has a 4-byte hole behind `depth` whose bytes are whatever the caller's memory held. The blocks are
+  // keyed by their contents (next line), not by the array's address.
+  key_put(key, dec->depth);
+  const void* dec_ptrs[] = {dec->adaln_w, dec->adaln_b, dec->patch_w, dec->patch_b, dec->head_w, dec->head_b};
+  key_put(key, dec_ptrs);
   for (int b = 0; b < dec->depth; ++b) key_put(key, dec->blocks[b]);
   for (int i = 0; i < steps; ++i) key_put(key, sched[i]);
   const void* ptrs[] = {zc, temb, x, ws_a, ws_u, ws_h, ws_f, ws_g, ws_mod, (const void*)st};
