@@ -1,14 +1,11 @@
-// C ABI of libnova_hip.so (declared in include/nova_hip.h): argument checks, error record,
-// and the composite launch sequences (ViT block stack, diffusion-MLP denoise loop).
+// C ABI of libnova_hip.so (include/nova_hip.h): the error and profiling records, the single-kernel wrappers with their argument checks and the ViT
+// block stacks. The denoising loop, its hipGraph cache and the nova_debug_*_graphs entries are denoise.hip. Both check with nova_internal.h's macros.
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <atomic>
 #include <cmath>
-#include <cstdlib>
 #include <mutex>
-#include <string>
-#include <unordered_map>
 #include <utility>
 #include <vector>
 #include "common.h"
@@ -39,8 +36,10 @@ static std::mutex g_prof_mu;  // the record list is shared by all calling thread
 static std::vector<ProfRec> g_prof;
 static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_prof_pool;
 
+bool prof_enabled() { return g_prof_on.load(std::memory_order_relaxed); }
+
 ProfScope::ProfScope(int slot, double work, hipStream_t s) : idx(-1), st(s) {
-  if (!g_prof_on.load(std::memory_order_relaxed)) return;
+  if (!prof_enabled()) return;
   std::lock_guard<std::mutex> lk(g_prof_mu);
   ProfRec r;
   if (!g_prof_pool.empty()) {
@@ -62,24 +61,6 @@ ProfScope::~ProfScope() {
   if (idx < (int)g_prof.size()) (void)hipEventRecord(g_prof[idx].b, st);
 }
 
-static inline bool bad_dtype(int dtype) { return dtype != NOVA_F32 && dtype != NOVA_BF16 && dtype != NOVA_F16; }
-static inline size_t esize(int dtype) { return dtype_is16(dtype) ? 2 : 4; }
-
-}  // namespace nova
-
-using namespace nova;
-
-#define NOVA_REQUIRE(cond, code, ...) \
-  do {                                \
-    if (!(cond)) return set_error(code, __VA_ARGS__); \
-  } while (0)
-#define NOVA_TRY(expr)        \
-  do {                        \
-    const int rc_ = (expr);   \
-    if (rc_ != 0) return rc_; \
-  } while (0)
-
-namespace nova {
 // Host-side launch state is per calling thread (ctypes releases the GIL during a call): the walk direction is set by a
 // composite for the launches it issues itself and restored when it returns, on every path.
 static thread_local bool g_walk_rev = false;
@@ -91,7 +72,15 @@ void walk_set_alternate(int on) { g_walk_alternate = on; }
 #else
 constexpr int g_walk_alternate = 1;
 #endif
+// every launch of a block stack walks its row tiles in the opposite direction of the previous one (fresh-first reads, common.h)
+struct Walk {
+  int k = 0;
+  void next() { walk_reverse(g_walk_alternate && (k++ & 1)); }
+  ~Walk() { walk_reverse(false); }
+};
 }  // namespace nova
+
+using namespace nova;
 
 extern "C" {
 
@@ -292,12 +281,7 @@ static int vit_blocks(const nova_vit_block* blocks, int nblocks, void* x, int S,
   const size_t es = esize(dtype);
   const float scale = 1.0f / sqrtf((float)hd);
   const char* qkv = static_cast<const char*>(ws_qkv);
-  // every launch walks its row tiles in the opposite direction of the previous one (fresh-first reads, common.h)
-  struct Walk {
-    int k = 0;
-    void next() { walk_reverse(g_walk_alternate && (k++ & 1)); }
-    ~Walk() { walk_reverse(false); }
-  } walk;
+  Walk walk;
   for (int i = 0; i < nblocks; ++i) {
     const nova_vit_block& b = blocks[i];
     // bf16 / f16: the softmax scale (in the exp2 domain) is folded into q by the QKV epilogue, before the 16-bit rounding
@@ -384,11 +368,7 @@ int nova_vit_blocks_forward_fp8(const nova_vit_block* blocks, const nova_vit_blo
   if (M == 0 || nblocks == 0) return 0;
   const float scale = 1.0f / sqrtf((float)hd);
   const char* qkv = static_cast<const char*>(ws_qkv);
-  struct Walk {
-    int k = 0;
-    void next() { walk_reverse(g_walk_alternate && (k++ & 1)); }
-    ~Walk() { walk_reverse(false); }
-  } walk;
+  Walk walk;
   NOVA_TRY(quantize_rows_fp8(x, ws_x8, ws_xs, M, D, st));  // the stack's input rows; later ones come from the LN kernels
   for (int i = 0; i < nblocks; ++i) {
     const nova_vit_block& b = blocks[i];
@@ -566,264 +546,9 @@ int nova_modulate_rows(const void* x, const void* mod, void* out, long rows, int
   return modulate_rows(x, mod, out, rows, D, dtype, (hipStream_t)stream);
 }
 
-}  // extern "C"
-
-namespace nova {
-
-// The launch sequence of one AR step's denoising loop (called directly, or once under stream capture: see below).
-static int decoder_denoise_launches(const nova_decoder* dec, const void* zc, const void* temb, float* x, const nova_sampler_step* sched,
-                                    const float* noise, float renorm, float* echo_energy, int steps, int S, int B, int n, int P, int D,
-                                    void* ws_a, void* ws_u, void* ws_h, void* ws_f, void* ws_g, void* ws_mod, float* ws_v, int mod_steps,
-                                    int dtype, hipStream_t st, float* echo_rows = nullptr, const float* echo_noise = nullptr, int Ne = 0) {
-  const bool do_renorm = renorm < 1.0f;
-  const size_t es = esize(dtype);
-  const int depth = dec->depth;
-  const long mod_ld = (long)(3 * depth + 2) * D;
-  const size_t nP = (size_t)B * n * P;
-  NOVA_REQUIRE(mod_steps == 1 || mod_steps == steps, NOVA_ERR_ARG, "decoder_denoise: mod_steps must be 1 or steps");
-  // The whole plan is checked before the first launch: a refused call leaves x (and the echo energy / rows) as they were, on the direct
-  // path as under capture. The loop below used to check step i after steps 0 .. i-1 had been launched.
-  NOVA_REQUIRE(P >= 1 && P <= 64, NOVA_ERR_SHAPE, "decoder_denoise: patch vector length %d unsupported", P);
-  for (int i = 0; i < steps; ++i) {
-    const nova_sampler_step& s = sched[i];
-    const int cfg = s.guidance > 1.0f ? 1 : 0;
-    NOVA_REQUIRE(s.extra_kind >= 0 && s.extra_kind <= 2, NOVA_ERR_ARG, "decoder_denoise: extra_kind must be 0, 1 or 2");
-    const int passes = cfg ? (s.extra_kind ? 3 : 2) : 1;
-    NOVA_REQUIRE(S >= passes * B, NOVA_ERR_SHAPE, "decoder_denoise: step %d needs %d guidance passes but S = %d, B = %d", i, passes, S, B);
-    // the scalar echo energy follows the Euler step only, on the steps without guidance (guidance_trunc) as well: they scale it too
-    NOVA_REQUIRE(!do_renorm || echo_rows || (s.kx == 0.f && s.kv == 1.f && s.cx == 1.f && s.sigma == 0.f && s.clip <= 0.f),
-                 NOVA_ERR_ARG, "decoder_denoise: guidance renorm with a scalar echo energy holds for the flow-matching Euler step only "
-                 "(other samplers: nova_decoder_denoise_echo with the echo rows)");
-  }
-  // mod_steps == steps: the AdaLN projections of ALL steps in one GEMM ahead of the loop (M = steps * S * n rows: the large-M
-  // kernel at ~2.5x the rate of the per-step small-M launches, and two launches fewer per step). Rows are laid out per
-  // step for the full S sequences; a step that runs fewer guidance passes (guidance_trunc) reads its leading rows.
-  const bool hoist = mod_steps == steps && steps > 1;
-  const long rows_all = (long)S * n;
-  if (hoist) {
-    NOVA_TRY(silu_add_steps(zc, temb, ws_a, rows_all, steps, D, dtype, st));
-    NOVA_TRY(gemm_bias_act(ws_a, dec->adaln_w, dec->adaln_b, ws_mod, (int)(rows_all * steps), (int)mod_ld, D, NOVA_ACT_NONE, dtype, st));
-  }
-  void* const ws_mod_base = ws_mod;
-  for (int i = 0; i < steps; ++i) {
-    const SamplerStep sp{sched[i].guidance, sched[i].kx,    sched[i].kv,          sched[i].clip,      sched[i].c0,
-                         sched[i].cx,       sched[i].sigma, sched[i].extra_scale, sched[i].extra_kind};
-    const int cfg = sp.guidance > 1.0f ? 1 : 0;
-    const int passes = cfg ? (sp.extra_kind ? 3 : 2) : 1;
-    const int Se = passes * B;
-    const long rows = (long)Se * n;
-    if (hoist) {
-      ws_mod = static_cast<char*>(ws_mod_base) + (size_t)i * rows_all * mod_ld * es;
-    } else {
-      NOVA_TRY(silu_add_rows(zc, static_cast<const char*>(temb) + (size_t)i * D * es, ws_a, rows, D, dtype, st));
-      NOVA_TRY(gemm_bias_act(ws_a, dec->adaln_w, dec->adaln_b, ws_mod, (int)rows, (int)mod_ld, D, NOVA_ACT_NONE, dtype, st));
-    }
-    NOVA_TRY(patch_embed_rows(x, dec->patch_w, dec->patch_b, ws_u, Se, B, n, P, D, dtype, st));
-    // Per block: m1 (modulate -> h), fc1 + SiLU, fc2, m2 (gated norm + residual -> u). Where the small-M kernel does not take m1 + fc1 as one
-    // launch (more than ~320 rows: every step of the batch-32 workload but the first few), m2 of block b and m1 of block b + 1 are ONE row pass
-    // (row_norm_chain: u is written, h comes out of the same registers; bit-identical to the two launches), so a block is 3 launches instead of 4.
-    const bool m1_fused = gemm_modulate_fused((int)rows, D, D, dtype);  // m1 rides inside the fc1 launch (skinny.hip)
-    const bool chain = !m1_fused && dtype_is16(dtype);
-    for (int b = 0; b < depth; ++b) {
-      const nova_mlp_block& blk = dec->blocks[b];
-      RowNormArgs m1{ws_u, ws_h, nullptr, nullptr, ws_mod, mod_ld, b * 3 * D, b * 3 * D + D, -1, nullptr, nullptr, rows, D, 1e-6f};
-      if (chain && b > 0) {
-        NOVA_TRY(gemm_bias_act(ws_h, blk.fc1_w, blk.fc1_b, ws_f, (int)rows, D, D, NOVA_ACT_SILU, dtype, st));  // h: the previous block's chain launch
-      } else {
-        NOVA_TRY(gemm_modulate_act(m1, blk.fc1_w, blk.fc1_b, ws_f, (int)rows, D, D, NOVA_ACT_SILU, dtype, st));  // one launch at small M
-      }
-      NOVA_TRY(gemm_bias_act(ws_f, blk.fc2_w, blk.fc2_b, ws_g, (int)rows, D, D, NOVA_ACT_NONE, dtype, st));
-      RowNormArgs m2{ws_g, ws_u, blk.norm2_w, blk.norm2_b, ws_mod, mod_ld, -1, -1, b * 3 * D + 2 * D, ws_u, nullptr, rows, D, 1e-5f};
-      RowNormArgs mf{ws_u, ws_h, nullptr, nullptr, ws_mod, mod_ld, depth * 3 * D, depth * 3 * D + D, -1, nullptr, nullptr, rows, D, 1e-6f};
-      if (b == depth - 1 && dtype_is16(dtype)) {
-        // last block: its gated norm + residual and the final layer's modulate in ONE row pass (x itself is not needed
-        // any more, so it is neither written nor read back); bit-identical to the two launches (rownorm.h)
-        NOVA_TRY(row_norm_chain(m2, mf, nullptr, dtype, st));
-      } else if (chain) {
-        RowNormArgs m1n{ws_u, ws_h, nullptr, nullptr, ws_mod, mod_ld, (b + 1) * 3 * D, (b + 1) * 3 * D + D, -1, nullptr, nullptr, rows, D, 1e-6f};
-        NOVA_TRY(row_norm_chain(m2, m1n, ws_u, dtype, st));  // u <- m2 in place (row-local), h <- m1 of the next block
-      } else {
-        NOVA_TRY(row_norm(m2, dtype, st));
-        if (b == depth - 1) NOVA_TRY(row_norm(mf, dtype, st));
-      }
-    }
-    const void* head_in = ws_h;
-    const float* nz = (noise && sp.sigma != 0.f) ? noise + (size_t)i * nP : nullptr;
-    if (do_renorm && echo_rows) {  // any sampler step: the echo rows are carried explicitly (rowops.hip: renorm_step_kernel)
-      const float* enz = (echo_noise && sp.sigma != 0.f) ? echo_noise + (size_t)i * B * Ne * P : nullptr;
-      if (cfg) {
-        float* extra = passes == 3 ? ws_v + 2 * nP : nullptr;
-        NOVA_TRY(head_cfg_step(head_in, dec->head_w, dec->head_b, x, nullptr, ws_v, ws_v + nP, extra, B, n, P, D, sp, 1, dtype, st));
-        NOVA_TRY(renorm_step(x, ws_v, ws_v + nP, extra, nz, echo_rows, enz, B, n * P, Ne * P, sp, renorm, 0, st));
-      } else {
-        NOVA_TRY(head_cfg_step(head_in, dec->head_w, dec->head_b, x, nz, nullptr, nullptr, nullptr, B, n, P, D, sp, 0, dtype, st));
-        NOVA_TRY(renorm_step(nullptr, nullptr, nullptr, nullptr, nullptr, echo_rows, enz, B, n * P, Ne * P, sp, renorm, 1, st));
-      }
-    } else if (do_renorm && cfg) {  // guidance_scaler.py:67-72: two small launches, norms over the whole sample
-      float* extra = passes == 3 ? ws_v + 2 * nP : nullptr;
-      NOVA_TRY(head_cfg_step(head_in, dec->head_w, dec->head_b, x, nullptr, ws_v, ws_v + nP, extra, B, n, P, D, sp, 1, dtype, st));
-      NOVA_TRY(renorm_euler(x, ws_v, ws_v + nP, extra, echo_energy, B, n, P, sp.c0, renorm, st));
-    } else {
-      NOVA_TRY(head_cfg_step(head_in, dec->head_w, dec->head_b, x, nz, nullptr, nullptr, nullptr, B, n, P, D, sp, 0, dtype, st));
-      // guidance switched off for this step (guidance_trunc): no renorm, but the echo rows still take the Euler step
-      if (do_renorm && echo_energy) NOVA_TRY(scale_vector(echo_energy, B, (1.0f + sp.c0) * (1.0f + sp.c0), st));
-    }
-  }
-  return 0;
-}
-
-
-// ---- hipGraph replay of the denoising loop.
-// One AR step issues 25 x (15 to 27) launches of 4-15 us kernels from one host thread. The sequence is a pure function
-// of the call's arguments, so it is captured
-// once per distinct argument set - pointers, shapes, the per-step sampler plan and the decoder's weight pointers all
-// go into the key - and replayed with one hipGraphLaunch afterwards. The engine keeps every buffer of the call at a
-// stable address (workspace slots), so from the second generation on every AR step of a fixed schedule is a replay.
-// Measured (tools/host_vs_gpu.py): the host thread's time in a batch-8 generation call drops 907 -> 795 ms; wall time is
-// unchanged at batch 8 and 32 (the device, not the launch rate, bounds both), the first call of a schedule pays ~3 ms
-// per captured graph.
-// Calls that read per-call tensors the engine allocates afresh (ancestral noise, guidance-renorm scratch) and profiled
-// runs (HIP-event brackets around launches) stay on the direct path.
-static std::atomic<long> g_graph_epoch{0};  // bumped by nova_debug_set_graphs(0): every thread drops its cache at its next call
-struct DecoderGraphs {
-  std::unordered_map<std::string, hipGraphExec_t> execs;
-  long captures = 0, replays = 0, epoch = 0;
-  ~DecoderGraphs() { clear(false); }  // thread exit / process teardown: the runtime may already be going down, no device call but the destroys
-  // A launch of one of these execs may still be queued or running on some stream (the host runs ahead of the device, and the caller
-  // drops the cache exactly when it is about to re-plan: a workspace that changed shape, graphs switched off): wait for the device
-  // before the execs and their kernel-argument storage go. Rare by construction (shape changes), so the wait is not a cost.
-  void clear(bool wait = true) {
-    if (wait && !execs.empty()) (void)hipDeviceSynchronize();
-    for (auto& kv : execs) (void)hipGraphExecDestroy(kv.second);
-    execs.clear();
-  }
-};
-static thread_local DecoderGraphs g_dec_graphs;
-static std::atomic<int> g_graphs_on{-1};  // -1: not decided yet (NOVA_GRAPHS env, default on)
-
-static bool graphs_enabled() {
-  int v = g_graphs_on.load(std::memory_order_relaxed);
-  if (v < 0) {
-    const char* e = getenv("NOVA_GRAPHS");
-    v = (e && e[0] == '0') ? 0 : 1;
-    g_graphs_on.store(v);
-  }
-  return v != 0;
-}
-
-template <typename T> static void key_put(std::string& k, const T& v) { k.append(reinterpret_cast<const char*>(&v), sizeof(T)); }
-
-}  // namespace nova
-
-extern "C" {
-
 int nova_debug_set_attn_variant(int variant) {
   NOVA_REQUIRE(attn_set_variant(variant) == 0, NOVA_ERR_ARG, "nova_debug_set_attn_variant: %d is not one of -1 .. 5", variant);
   return 0;
-}
-
-int nova_debug_set_graphs(int on) {
-  g_graphs_on.store(on ? 1 : 0);
-  if (!on) {  // the calling thread's graphs go now, every other thread's at its next nova_decoder_denoise (the caches are thread-local)
-    g_graph_epoch.fetch_add(1);
-    g_dec_graphs.clear();
-  }
-  return 0;
-}
-
-int nova_debug_drop_graphs(void) {
-  g_dec_graphs.clear();
-  return 0;
-}
-
-int nova_debug_graph_stats(long* captures, long* replays) {
-  if (captures) *captures = g_dec_graphs.captures;
-  if (replays) *replays = g_dec_graphs.replays;
-  return 0;
-}
-
-int nova_decoder_denoise(const nova_decoder* dec, const void* zc, const void* temb, float* x, const nova_sampler_step* sched,
-                         const float* noise, float renorm, float* echo_energy, int steps, int S, int B, int n, int P, int D,
-                         void* ws_a, void* ws_u, void* ws_h, void* ws_f, void* ws_g, void* ws_mod, float* ws_v, int mod_steps,
-                         int dtype, void* stream) {
-  NOVA_REQUIRE(!bad_dtype(dtype), NOVA_ERR_ARG, "decoder_denoise: bad dtype %d", dtype);
-  NOVA_REQUIRE(dec && zc && temb && x && sched && ws_a && ws_u && ws_h && ws_f && ws_g && ws_mod, NOVA_ERR_ARG,
-               "decoder_denoise: null pointer");
-  NOVA_REQUIRE(S == B || S == 2 * B || S == 3 * B, NOVA_ERR_SHAPE, "decoder_denoise: S must be B, 2B or 3B");
-  NOVA_REQUIRE(dec->depth >= 1 && dec->blocks, NOVA_ERR_ARG, "decoder_denoise: the decoder needs at least one block");
-  const bool do_renorm = renorm < 1.0f;
-  NOVA_REQUIRE(!do_renorm || (echo_energy && ws_v), NOVA_ERR_ARG, "decoder_denoise: renorm needs echo_energy and ws_v");
-  if (n == 0 || B == 0) return 0;
-  hipStream_t st = (hipStream_t)stream;
-  const bool direct = !graphs_enabled() || g_prof_on.load(std::memory_order_relaxed) || noise != nullptr || do_renorm || steps < 2;
-  if (direct)
-    return decoder_denoise_launches(dec, zc, temb, x, sched, noise, renorm, echo_energy, steps, S, B, n, P, D, ws_a, ws_u, ws_h, ws_f,
-                                    ws_g, ws_mod, ws_v, mod_steps, dtype, st);
-  if (const long e = g_graph_epoch.load(std::memory_order_relaxed); e != g_dec_graphs.epoch) {
-    g_dec_graphs.clear();
-    g_dec_graphs.epoch = e;
-  }
-  std::string key;
-  key.reserve(512 + sizeof(nova_sampler_step) * steps + sizeof(nova_mlp_block) * dec->depth);
-  // field by field: the struct has a 4-byte hole behind `depth` whose bytes are whatever the caller's memory held. The blocks are
-  // keyed by their contents (next line), not by the array's address.
-  key_put(key, dec->depth);
-  const void* dec_ptrs[] = {dec->adaln_w, dec->adaln_b, dec->patch_w, dec->patch_b, dec->head_w, dec->head_b};
-  key_put(key, dec_ptrs);
-  for (int b = 0; b < dec->depth; ++b) key_put(key, dec->blocks[b]);
-  for (int i = 0; i < steps; ++i) key_put(key, sched[i]);
-  const void* ptrs[] = {zc, temb, x, ws_a, ws_u, ws_h, ws_f, ws_g, ws_mod, (const void*)st};
-  key_put(key, ptrs);
-  const int ints[] = {steps, S, B, n, P, D, mod_steps, dtype, walk_is_reverse() ? 1 : 0, gemm_forced_tile(), skinny_forced_row_blocks()};
-  key_put(key, ints);
-  auto it = g_dec_graphs.execs.find(key);
-  if (it == g_dec_graphs.execs.end()) {
-    if (g_dec_graphs.execs.size() >= 2048) g_dec_graphs.clear();  // schedules come and go: start over rather than grow
-    if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) != hipSuccess) {
-      (void)hipGetLastError();
-      return decoder_denoise_launches(dec, zc, temb, x, sched, noise, renorm, echo_energy, steps, S, B, n, P, D, ws_a, ws_u, ws_h, ws_f,
-                                      ws_g, ws_mod, ws_v, mod_steps, dtype, st);
-    }
-    const int rc = decoder_denoise_launches(dec, zc, temb, x, sched, noise, renorm, echo_energy, steps, S, B, n, P, D, ws_a, ws_u, ws_h,
-                                            ws_f, ws_g, ws_mod, ws_v, mod_steps, dtype, st);
-    hipGraph_t graph = nullptr;
-    const hipError_t ec = hipStreamEndCapture(st, &graph);
-    if (rc != 0) {
-      if (graph) (void)hipGraphDestroy(graph);
-      return rc;
-    }
-    hipGraphExec_t exec = nullptr;
-    const hipError_t ei = (ec == hipSuccess && graph) ? hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) : ec;
-    if (graph) (void)hipGraphDestroy(graph);
-    if (ei != hipSuccess || !exec) {  // nothing has executed yet (the launches above were only recorded): run them directly
-      (void)hipGetLastError();
-      return decoder_denoise_launches(dec, zc, temb, x, sched, noise, renorm, echo_energy, steps, S, B, n, P, D, ws_a, ws_u, ws_h, ws_f,
-                                      ws_g, ws_mod, ws_v, mod_steps, dtype, st);
-    }
-    it = g_dec_graphs.execs.emplace(std::move(key), exec).first;
-    ++g_dec_graphs.captures;
-  } else {
-    ++g_dec_graphs.replays;
-  }
-  const hipError_t el = hipGraphLaunch(it->second, st);
-  NOVA_REQUIRE(el == hipSuccess, NOVA_ERR_LAUNCH, "decoder_denoise: hipGraphLaunch failed: %s", hipGetErrorString(el));
-  return 0;
-}
-
-int nova_decoder_denoise_echo(const nova_decoder* dec, const void* zc, const void* temb, float* x, const nova_sampler_step* sched,
-                              const float* noise, float renorm, float* echo_rows, const float* echo_noise, int Ne, int steps, int S, int B,
-                              int n, int P, int D, void* ws_a, void* ws_u, void* ws_h, void* ws_f, void* ws_g, void* ws_mod, float* ws_v,
-                              int mod_steps, int dtype, void* stream) {
-  NOVA_REQUIRE(!bad_dtype(dtype), NOVA_ERR_ARG, "decoder_denoise_echo: bad dtype %d", dtype);
-  NOVA_REQUIRE(dec && zc && temb && x && sched && ws_a && ws_u && ws_h && ws_f && ws_g && ws_mod, NOVA_ERR_ARG,
-               "decoder_denoise_echo: null pointer");
-  NOVA_REQUIRE(S == B || S == 2 * B || S == 3 * B, NOVA_ERR_SHAPE, "decoder_denoise_echo: S must be B, 2B or 3B");
-  NOVA_REQUIRE(dec->depth >= 1 && dec->blocks, NOVA_ERR_ARG, "decoder_denoise_echo: the decoder needs at least one block");
-  NOVA_REQUIRE(renorm < 1.0f && echo_rows && ws_v && Ne >= 0, NOVA_ERR_ARG,
-               "decoder_denoise_echo: for guidance_renorm < 1 with the echo rows given (else: nova_decoder_denoise)");
-  if (n == 0 || B == 0) return 0;
-  return decoder_denoise_launches(dec, zc, temb, x, sched, noise, renorm, nullptr, steps, S, B, n, P, D, ws_a, ws_u, ws_h, ws_f, ws_g, ws_mod,
-                                  ws_v, mod_steps, dtype, (hipStream_t)stream, echo_rows, echo_noise, Ne);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// Internal declarations shared by the kernel translation units and the C ABI (capi.hip).
+// Internal declarations shared by the kernel translation units and the C ABI (capi.hip, denoise.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -17,11 +17,15 @@ template <typename F> inline auto dispatch_dtype(int dtype, F&& f) {
   return dtype == NOVA_BF16 ? f(bf16_t{}) : dtype == NOVA_F16 ? f(f16_t{}) : f(float{});
 }
 template <typename F> inline auto dispatch_half(int dtype, F&& f) { return dtype == NOVA_F16 ? f(f16_t{}) : f(bf16_t{}); }
+inline bool bad_dtype(int dtype) { return dtype != NOVA_F32 && dtype != NOVA_BF16 && dtype != NOVA_F16; }
+inline size_t esize(int dtype) { return dtype_is16(dtype) ? 2 : 4; }
 
 // thread-local last-error record; returns `code` so callers can `return set_error(...)`.
 int set_error(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 // hipGetLastError() -> NOVA_ERR_LAUNCH (+ message) or 0. Never synchronises.
 int check_launch(const char* what);
+#define NOVA_REQUIRE(cond, code, ...) do { if (!(cond)) return set_error(code, __VA_ARGS__); } while (0)
+#define NOVA_TRY(expr) do { const int rc_ = (expr); if (rc_ != 0) return rc_; } while (0)
 
 // ---- optional per-kernel timing with HIP events on the launch stream (capi.hip). Slots: one per
 // kernel family; `work` = algorithmic FLOPs (or bytes) of the launch. No-ops unless enabled.
@@ -39,6 +43,7 @@ struct ProfScope {
   int idx;
   hipStream_t st;
 };
+bool prof_enabled();  // nova_prof_enable(1) is in force: launches carry event brackets (and the denoising loop is not captured)
 
 // ---- gemm.hip, gemm256.hip: the epilogue of out = epi(A W^T + bias), one vocabulary for every GEMM structure
 struct GemmEpi {
@@ -179,11 +184,7 @@ int silu_add_steps(const void* a, const void* vecs, void* out, long rows, int nv
 int timestep_freq(const float* t, const float* freq, void* out, int n, int freq_dim, int dtype, hipStream_t st);
 int patch_embed_rows(const float* x, const void* w, const float* bias, void* out, int S, int B, int n, int P, int D,
                      int dtype, hipStream_t st);
-struct SamplerStep {  // == nova_sampler_step (include/nova_hip.h)
-  float guidance, kx, kv, clip, c0, cx, sigma;
-  float extra_scale;  // 3-pass guidance: image / spatiotemporal guidance scale
-  int extra_kind;     // 0 = 2-pass, 1 = image guidance, 2 = spatiotemporal guidance (third row block of h)
-};
+using SamplerStep = nova_sampler_step;  // the kernels take the ABI's struct itself (include/nova_hip.h)
 int head_cfg_step(const void* h, const void* w, const float* bias, float* x, const float* noise, float* vhat, float* cond,
                   float* extra, int B, int n, int P, int D, const SamplerStep& sp, int defer, int dtype, hipStream_t st);
 int scale_vector(float* v, int n, float f, hipStream_t st);

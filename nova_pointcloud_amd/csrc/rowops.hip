@@ -500,6 +500,15 @@ int patch_embed_rows(const float* x, const void* w, const float* bias, void* out
   return check_launch("patch_embed_rows");
 }
 
+// The sampler step of element e (nova_sampler_step, include/nova_hip.h), for the predicted rows and the echo rows alike
+__device__ __forceinline__ float sampler_step(const SamplerStep& sp, float xo, float v, const float* noise, long e) {
+  float x0 = sp.kx * xo + sp.kv * v;
+  if (sp.clip > 0.f) x0 = fminf(fmaxf(x0, -sp.clip), sp.clip);
+  float xn = sp.c0 * x0 + sp.cx * xo;
+  if (noise) xn += sp.sigma * noise[e];
+  return xn;
+}
+
 // Head projection + guidance combine + one sampler step for the n tokens of this AR step:
 //   pc = Wh h[b][j] + bh, pu = Wh h[B + b][j] + bh, (3-pass: p3 = Wh h[2B + b][j] + bh)
 //   2-pass (guidance_scaler.py:86-87):            v = pu + g (pc - pu)
@@ -560,13 +569,7 @@ __global__ __launch_bounds__(256) void head_cfg_step_kernel(const T* __restrict_
         cond[e] = ac;
         if (extra) extra[e] = ex;
       } else {
-        vv += ex;
-        const float xo = x[e];
-        float x0 = sp.kx * xo + sp.kv * vv;
-        if (sp.clip > 0.f) x0 = fminf(fmaxf(x0, -sp.clip), sp.clip);
-        float xn = sp.c0 * x0 + sp.cx * xo;
-        if (noise) xn += sp.sigma * noise[e];
-        x[e] = xn;
+        x[e] = sampler_step(sp, x[e], vv + ex, noise, e);
       }
     }
   }
@@ -590,6 +593,18 @@ int head_cfg_step(const void* h, const void* w, const float* bias, float* x, con
   return check_launch("head_cfg_step");
 }
 
+// The sums behind the guidance-renorm ratio of the two kernels below, in ONE order (recorded bits): wave_sum, the four wave sums through
+// red[0..3], after the caller's barrier (r0 + r1) + (r2 + r3), the echo term E last. block_sum_fixed (pointset_common.h) adds the waves
+// left to right: other bits.
+template <typename... V> __device__ __forceinline__ void wave_sums_put(float (*red)[4], V... v) {
+  const float s[] = {wave_sum(v)...};
+  if ((threadIdx.x & 63) == 0) for (unsigned k = 0; k < sizeof...(V); ++k) red[k][threadIdx.x >> 6] = s[k];
+}
+__device__ __forceinline__ float sum4(const float* red) { return (red[0] + red[1]) + (red[2] + red[3]); }
+__device__ __forceinline__ float renorm_ratio(const float* red_v, const float* red_c, float E, float renorm) {
+  return fminf(fmaxf(sqrtf(sum4(red_c) + E) / sqrtf(sum4(red_v) + E), renorm), 1.0f);
+}
+
 // Guidance renormalisation (guidance_scaler.py:67-72) for the flow-matching Euler step. The reference takes the
 // norms over ALL N rows of a sample: the n predicted rows plus the rows that merely echo the current x_t. The
 // echo rows never leave this kernel's view: their squared norm E_b is a scalar that evolves with the same step
@@ -601,7 +616,7 @@ __global__ __launch_bounds__(256) void renorm_euler_kernel(float* __restrict__ x
                                                           const float* __restrict__ cond, const float* __restrict__ extra,
                                                           float* __restrict__ echo, int nP, float dt, float renorm) {
   __shared__ float red[2][4];
-  const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int b = blockIdx.x;
   const float* vb = vhat + (long)b * nP;
   const float* cb = cond + (long)b * nP;
   float sv = 0.f, sc = 0.f;
@@ -609,14 +624,10 @@ __global__ __launch_bounds__(256) void renorm_euler_kernel(float* __restrict__ x
     sv += vb[i] * vb[i];
     sc += cb[i] * cb[i];
   }
-  sv = wave_sum(sv);
-  sc = wave_sum(sc);
-  if (lane == 0) { red[0][wv] = sv; red[1][wv] = sc; }
+  wave_sums_put(red, sv, sc);
   __syncthreads();
   const float E = echo[b];
-  const float nx = sqrtf((red[0][0] + red[0][1]) + (red[0][2] + red[0][3]) + E);
-  const float nc = sqrtf((red[1][0] + red[1][1]) + (red[1][2] + red[1][3]) + E);
-  const float ratio = fminf(fmaxf(nc / nx, renorm), 1.0f);
+  const float ratio = renorm_ratio(red[0], red[1], E, renorm);
   for (int i = threadIdx.x; i < nP; i += 256) x[(long)b * nP + i] += dt * (ratio * vb[i] + (extra ? extra[(long)b * nP + i] : 0.f));
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -638,7 +649,7 @@ __global__ __launch_bounds__(256) void renorm_step_kernel(float* __restrict__ x,
                                                          float* __restrict__ echo, const float* __restrict__ echo_noise, int nP, int eP,
                                                          SamplerStep sp, float renorm, int echo_only) {
   __shared__ float red[3][4];
-  const int b = blockIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int b = blockIdx.x;
   float* eb = echo + (long)b * eP;
   float ratio = 1.0f;
   if (!echo_only) {
@@ -650,33 +661,20 @@ __global__ __launch_bounds__(256) void renorm_step_kernel(float* __restrict__ x,
       sc += cb[i] * cb[i];
     }
     for (int i = threadIdx.x; i < eP; i += 256) se += eb[i] * eb[i];
-    sv = wave_sum(sv);
-    sc = wave_sum(sc);
-    se = wave_sum(se);
-    if (lane == 0) { red[0][wv] = sv; red[1][wv] = sc; red[2][wv] = se; }
+    wave_sums_put(red, sv, sc, se);
     __syncthreads();
-    const float E = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]);
-    const float nx = sqrtf((red[0][0] + red[0][1]) + (red[0][2] + red[0][3]) + E);
-    const float nc = sqrtf((red[1][0] + red[1][1]) + (red[1][2] + red[1][3]) + E);
-    ratio = fminf(fmaxf(nc / nx, renorm), 1.0f);
+    ratio = renorm_ratio(red[0], red[1], sum4(red[2]), renorm);
     __syncthreads();  // every thread has read the echo rows before any of them is overwritten below
   }
-  auto step = [&](float xo, float v, const float* nz, long e) {
-    float x0 = sp.kx * xo + sp.kv * v;
-    if (sp.clip > 0.f) x0 = fminf(fmaxf(x0, -sp.clip), sp.clip);
-    float xn = sp.c0 * x0 + sp.cx * xo;
-    if (nz) xn += sp.sigma * nz[e];
-    return xn;
-  };
   if (!echo_only) {
     for (int i = threadIdx.x; i < nP; i += 256) {
       const long e = (long)b * nP + i;
-      x[e] = step(x[e], ratio * vhat[e] + (extra ? extra[e] : 0.f), noise, e);
+      x[e] = sampler_step(sp, x[e], ratio * vhat[e] + (extra ? extra[e] : 0.f), noise, e);
     }
   }
   for (int i = threadIdx.x; i < eP; i += 256) {
     const long e = (long)b * eP + i;
-    echo[e] = step(echo[e], ratio * echo[e], echo_noise, e);
+    echo[e] = sampler_step(sp, echo[e], ratio * echo[e], echo_noise, e);
   }
 }
 

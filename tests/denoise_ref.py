@@ -1,6 +1,7 @@
 """A float64 restatement of the denoising loop (`nova_decoder_denoise`, `nova_decoder_denoise_echo`) and the plumbing to
 call the two entry points directly. A plain helper module (like golden_util.py), shared by test_denoise_restatement_cpu.py,
-which pins the restatement against the project's PyTorch modules without a GPU, and test_gpu_denoise_loop.py.
+which pins the restatement against the project's PyTorch modules without a GPU, test_gpu_denoise_loop.py and the recorded
+bits (golden/make_golden_denoise_bits.py); the last two build their cases from SHAPES, BRANCHES and draw_inputs below.
 
 `denoise_ref` is written from the definitions in include/nova_hip.h (`nova_sampler_step`, `nova_decoder_denoise`,
 `nova_decoder_denoise_echo`) and diffnext/models/diffusion_mlp.py, not from the kernels: one plain loop, all arithmetic in
@@ -9,6 +10,7 @@ float64, one code path for every shape. The sampler step's `clip` is a number in
 import collections
 import ctypes
 import re
+import zlib
 
 import numpy as np
 import torch
@@ -265,3 +267,67 @@ def ddpm_coefs(steps, prediction_type):
     from nova_pointcloud_amd.diffnext.schedulers import DDPMScheduler
 
     return engine.sampler_plan(DDPMScheduler(prediction_type=prediction_type), steps)[1]
+
+
+# ---------------------------------------------------------------------------------------------
+# the cases of the GPU tests: shapes, sampler branches and the inputs / plan of one draw. One definition for the numerics
+# (test_gpu_denoise_loop.py) and the recorded bits (golden/make_golden_denoise_bits.py, test_gpu_denoise_bits.py)
+# ---------------------------------------------------------------------------------------------
+SHAPES = {"ragged": (3, 7, 3), "cross": (2, 100, 3), "p12": (2, 5, 12), "p64": (1, 3, 64)}  # (B, n, P): test_gpu_denoise_loop.py says why
+
+# name -> sampler ("euler" or a DDPM prediction type), guidance, and what differs from the plain 2-pass call
+#   trunc: the last two steps run at guidance 1; extra: (extra_kind, extra_scale); energy: echo energy per predicted value
+#   (the scalar entry); Ne: echo rows (the echo entry); regime: where the UNCLAMPED ratio of the reference must lie at least once
+BRANCHES = {
+    "euler_nocfg": dict(sampler="euler", g=1.0, passes=1),
+    "euler_cfg": dict(sampler="euler", g=4.0),
+    "euler_trunc": dict(sampler="euler", g=4.0, trunc=True),
+    "renorm_floor_zero_energy": dict(sampler="euler", g=8.0, renorm=0.3, energy=0.0, regime="below"),
+    "renorm_inside": dict(sampler="euler", g=4.0, trunc=True, renorm=0.3, energy=1.0, regime="inside"),
+    "renorm_above": dict(sampler="euler", g=3.0, extra=(1, 1.5), third_is_cond=True, renorm=0.3, energy=0.1, regime="above"),
+    "image": dict(sampler="euler", g=3.0, trunc=True, extra=(1, 1.5)),
+    "image_renorm": dict(sampler="euler", g=3.0, trunc=True, extra=(1, 1.5), renorm=0.3, energy=1.0),
+    "spatiotemporal": dict(sampler="euler", g=3.0, trunc=True, extra=(2, 1.5)),
+    "spatiotemporal_renorm": dict(sampler="euler", g=3.0, trunc=True, extra=(2, 1.5), renorm=0.3, energy=1.0),
+    "ddpm_epsilon": dict(sampler="epsilon", g=4.0, noise=True),
+    "ddpm_v": dict(sampler="v_prediction", g=4.0, noise=True),
+    "ddpm_sample": dict(sampler="sample", g=4.0, noise=True),
+    "echo_ne0": dict(sampler="epsilon", g=4.0, noise=True, trunc=True, renorm=0.3, Ne=0),
+    "echo_ne9": dict(sampler="epsilon", g=4.0, noise=True, trunc=True, renorm=0.3, Ne=9),
+    "echo_ne100": dict(sampler="v_prediction", g=4.0, noise=True, trunc=True, renorm=0.3, Ne=100),
+    "echo_spatiotemporal": dict(sampler="sample", g=3.0, noise=True, trunc=True, extra=(2, 1.5), renorm=0.3, Ne=9),
+}
+for _name in ("ddpm_epsilon", "ddpm_v", "ddpm_sample", "echo_ne0", "echo_ne9", "echo_ne100"):
+    # g = 1.5: at g = 4 the clamp's survivors of the first DDPM steps carry errors no float32 run keeps below the f32 bound (case_is_fit)
+    BRANCHES[_name + "_clip"] = dict(BRANCHES[_name], clip=1.0, g=1.5)
+GRAPH_BRANCHES = [k for k, v in BRANCHES.items() if not v.get("noise") and v.get("renorm", 1.0) >= 1]  # what may be captured
+
+
+
+def weights_seed(D, depth, P):
+    """The seed of a case's decoder weights (make_weights / make_decoder)."""
+    return 1000 + D + depth + P
+
+
+def draw_inputs(shape, D, branch, depth, steps, draw):
+    """Inputs and plan of one case (CPU tensors; no reference): draw `draw` of the seeded generator."""
+    B, n, P = SHAPES[shape]
+    spec = BRANCHES[branch]
+    extra_kind, extra_scale = spec.get("extra", (0, 0.0))
+    passes = spec.get("passes", 3 if extra_kind else 2)
+    Ne = spec.get("Ne")
+    inp = make_inputs(B, n, P, D, passes, steps, seed=zlib.crc32(f"{shape}/{D}/{branch}/{draw}".encode()), Ne=Ne or 0)
+    if spec.get("third_is_cond"):  # image guidance with the third pass equal to the cond pass: v-hat = u exactly, ratio |c| / |u|
+        inp["zc"] = torch.cat([inp["zc"][: 2 * B * n], inp["zc"][: B * n]])
+    coefs = euler_coefs(steps) if spec["sampler"] == "euler" else ddpm_coefs(steps, spec["sampler"])
+    g = [spec["g"]] * steps
+    if spec.get("trunc"):
+        g[-2:] = [1.0] * len(g[-2:])
+    plan = make_plan(coefs, g, extra_scale, extra_kind, clip=spec.get("clip"))
+    renorm = spec.get("renorm", 1.0)
+    energy = None if "energy" not in spec else torch.full((B,), spec["energy"] * n * P) * (1 + 0.25 * torch.arange(B))
+    c = dict(shape=shape, D=D, branch=branch, depth=depth, steps=steps, B=B, n=n, P=P, passes=passes, plan=plan, renorm=renorm,
+             zc=inp["zc"], temb=inp["temb"], x=inp["x"], noise=inp["noise"] if spec.get("noise") else None, energy=energy,
+             echo_rows=inp["echo_rows"] if Ne is not None else None, echo_noise=inp["echo_noise"] if Ne is not None else None,
+             regime=spec.get("regime"), clip=spec.get("clip", 0.0), draw=draw)
+    return c

@@ -56,7 +56,6 @@ f32, largest max-abs error: 4.1e-5 (echo_ne0_clip, cross D=768; plain CPU float3
 """
 import ctypes
 import functools
-import zlib
 
 import pytest
 import torch
@@ -72,36 +71,11 @@ FACTOR = 3.0
 STEPS, DEPTH = 4, 3
 MAX_DRAWS = 16  # inputs are redrawn until case_is_fit() holds on the float64 reference alone
 POOL = 4  # input draws behind the 16-bit yardstick of the echo outputs (pooled_echo_yardstick)
-SHAPES = {"ragged": (3, 7, 3), "cross": (2, 100, 3), "p12": (2, 5, 12), "p64": (1, 3, 64)}
 NOVA_ERR_ARG, NOVA_ERR_SHAPE = -1, -2
 
-# name -> sampler ("euler" or a DDPM prediction type), guidance, and what differs from the plain 2-pass call
-#   trunc: the last two steps run at guidance 1; extra: (extra_kind, extra_scale); energy: echo energy per predicted value
-#   (the scalar entry); Ne: echo rows (the echo entry); regime: where the UNCLAMPED ratio of the reference must lie at least once
-BRANCHES = {
-    "euler_nocfg": dict(sampler="euler", g=1.0, passes=1),
-    "euler_cfg": dict(sampler="euler", g=4.0),
-    "euler_trunc": dict(sampler="euler", g=4.0, trunc=True),
-    "renorm_floor_zero_energy": dict(sampler="euler", g=8.0, renorm=0.3, energy=0.0, regime="below"),
-    "renorm_inside": dict(sampler="euler", g=4.0, trunc=True, renorm=0.3, energy=1.0, regime="inside"),
-    "renorm_above": dict(sampler="euler", g=3.0, extra=(1, 1.5), third_is_cond=True, renorm=0.3, energy=0.1, regime="above"),
-    "image": dict(sampler="euler", g=3.0, trunc=True, extra=(1, 1.5)),
-    "image_renorm": dict(sampler="euler", g=3.0, trunc=True, extra=(1, 1.5), renorm=0.3, energy=1.0),
-    "spatiotemporal": dict(sampler="euler", g=3.0, trunc=True, extra=(2, 1.5)),
-    "spatiotemporal_renorm": dict(sampler="euler", g=3.0, trunc=True, extra=(2, 1.5), renorm=0.3, energy=1.0),
-    "ddpm_epsilon": dict(sampler="epsilon", g=4.0, noise=True),
-    "ddpm_v": dict(sampler="v_prediction", g=4.0, noise=True),
-    "ddpm_sample": dict(sampler="sample", g=4.0, noise=True),
-    "echo_ne0": dict(sampler="epsilon", g=4.0, noise=True, trunc=True, renorm=0.3, Ne=0),
-    "echo_ne9": dict(sampler="epsilon", g=4.0, noise=True, trunc=True, renorm=0.3, Ne=9),
-    "echo_ne100": dict(sampler="v_prediction", g=4.0, noise=True, trunc=True, renorm=0.3, Ne=100),
-    "echo_spatiotemporal": dict(sampler="sample", g=3.0, noise=True, trunc=True, extra=(2, 1.5), renorm=0.3, Ne=9),
-}
-for _name in ("ddpm_epsilon", "ddpm_v", "ddpm_sample", "echo_ne0", "echo_ne9", "echo_ne100"):
-    # g = 1.5: at g = 4 the clamp's survivors of the first DDPM steps carry errors no float32 run keeps below the f32 bound (case_is_fit)
-    BRANCHES[_name + "_clip"] = dict(BRANCHES[_name], clip=1.0, g=1.5)
+SHAPES, BRANCHES = R.SHAPES, R.BRANCHES  # one definition with the recorded bits (test_gpu_denoise_bits.py)
 RENORM_BRANCHES = [k for k, v in BRANCHES.items() if v.get("renorm", 1.0) < 1]
-GRAPH_BRANCHES = [k for k, v in BRANCHES.items() if not v.get("noise") and v.get("renorm", 1.0) >= 1]  # what may be captured
+GRAPH_BRANCHES = R.GRAPH_BRANCHES  # what may be captured
 
 
 def bits(t):
@@ -120,7 +94,7 @@ def errs(got, ref):
 
 @functools.lru_cache(maxsize=None)
 def weights(D, depth, P):
-    return R.make_decoder(D, depth, P, None, seed=1000 + D + depth + P)[0]
+    return R.make_decoder(D, depth, P, None, seed=R.weights_seed(D, depth, P))[0]
 
 
 _packs = {}
@@ -129,7 +103,7 @@ _packs = {}
 def pack_for(hip, D, depth, P, dtype):
     key = (D, depth, P, dtype)
     if key not in _packs:
-        _packs[key] = R.make_decoder(D, depth, P, dtype, seed=1000 + D + depth + P, hip=hip, device=DEV)[1]
+        _packs[key] = R.make_decoder(D, depth, P, dtype, seed=R.weights_seed(D, depth, P), hip=hip, device=DEV)[1]
     return _packs[key]
 
 
@@ -144,25 +118,7 @@ def case(shape, D, branch, depth=DEPTH, steps=STEPS):
 
 
 def draw_case(shape, D, branch, depth, steps, draw):
-    B, n, P = SHAPES[shape]
-    spec = BRANCHES[branch]
-    extra_kind, extra_scale = spec.get("extra", (0, 0.0))
-    passes = spec.get("passes", 3 if extra_kind else 2)
-    Ne = spec.get("Ne")
-    inp = R.make_inputs(B, n, P, D, passes, steps, seed=zlib.crc32(f"{shape}/{D}/{branch}/{draw}".encode()), Ne=Ne or 0)
-    if spec.get("third_is_cond"):  # image guidance with the third pass equal to the cond pass: v-hat = u exactly, ratio |c| / |u|
-        inp["zc"] = torch.cat([inp["zc"][: 2 * B * n], inp["zc"][: B * n]])
-    coefs = R.euler_coefs(steps) if spec["sampler"] == "euler" else R.ddpm_coefs(steps, spec["sampler"])
-    g = [spec["g"]] * steps
-    if spec.get("trunc"):
-        g[-2:] = [1.0] * len(g[-2:])
-    plan = R.make_plan(coefs, g, extra_scale, extra_kind, clip=spec.get("clip"))
-    renorm = spec.get("renorm", 1.0)
-    energy = None if "energy" not in spec else torch.full((B,), spec["energy"] * n * P) * (1 + 0.25 * torch.arange(B))
-    c = dict(shape=shape, D=D, branch=branch, depth=depth, steps=steps, B=B, n=n, P=P, passes=passes, plan=plan, renorm=renorm,
-             zc=inp["zc"], temb=inp["temb"], x=inp["x"], noise=inp["noise"] if spec.get("noise") else None, energy=energy,
-             echo_rows=inp["echo_rows"] if Ne is not None else None, echo_noise=inp["echo_noise"] if Ne is not None else None,
-             regime=spec.get("regime"), clip=spec.get("clip", 0.0), draw=draw)
+    c = R.draw_inputs(shape, D, branch, depth, steps, draw)
     c["ref"] = reference(c, None)
     return c
 
