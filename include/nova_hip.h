@@ -523,6 +523,87 @@ int nova_pointset_kernel_interpolate_bwd(const float* q, const float* p, const f
                                          const float* l, const float* g, float* gq, float* gp, float* gv,
                                          int S, int T, int N, int C, float scale, void* stream);
 
+/* Soft cluster pooling, forward and backward: for every cloud x [S, N, 3] (float32, finite) and K centres c, the K
+ * softmax(-distance / temperature)-weighted centroids out [S, K, 3] and the cluster masses mass [S, K] (float32). It is the
+ * soft clustering step both point-cloud models of the reference run on their gradient path,
+ * PointCloudTransformer.forward, diffnext/models/transformers/transformer_pointcloud_nova.py:465-487, and
+ * NOVAPointCloudTransformer.forward, :724-741 (torch.cdist(points, cluster_centers), softmax(-distances) over the centres,
+ * a Python loop over the 8 clusters forming (points * w).sum(1) / (w.sum(1) + 1e-8)), where PyTorch keeps the [B, N, 8]
+ * distances and weights and 8 [B, N, 3] products alive for the backward; the centres are a learnable parameter
+ * (cluster_centers [8, 3]), with the temperature (1 there) made a parameter. Neither pass stores anything of size N K.
+ * shared_centers != 0: c is [K, 3], the same for every cloud (the reference's parameter); otherwise c is [S, K, 3].
+ * nova_pointset_soft_cluster: for point i and centre k of one cloud, every operation rounded once to float32 and nothing
+ *   fused that is not written as fmaf, sqdist3 the expression of nova_pointset_knn:
+ *     d_k   = sqrtf(sqdist3(x_i, c_k))                   correctly rounded square root
+ *     m     = min_k d_k
+ *     e_k   = exp2f((m - d_k) * scale)                   scale = log2(e) / temperature in float32, made by the caller; the
+ *                                                        difference and the product rounded once each, exp2f the hardware's
+ *                                                        v_exp_f32 (1 ulp; results below 2^-126 become 0), as in
+ *                                                        nova_pointset_kernel_interpolate
+ *     L     = e_0, then L = L + e_k for k = 1 .. K-1 in that order;  r = 1 / L   (one IEEE division; L >= 1)
+ *     a_ik  = e_k * r
+ *     mass_k   = sum_i a_ik                              each step acc = acc + a_ik
+ *     num_k[j] = sum_i a_ik * x_i[j]                     each step acc = fmaf(a_ik, x_i[j], acc)
+ *     out[s, k, j] = num_k[j] / (mass_k + 1e-8f)         one rounded addition, one IEEE division; 1e-8f is the reference's
+ *                                                        constant (:480), part of the definition
+ *   Order of the two sums over i (part of the definition: it fixes the bits; it depends on N and K alone). The cloud is cut
+ *   into chunks of NOVA_SOFT_CLUSTER_CHUNK = 1024 consecutive points. Inside a chunk starting at point b, thread t of 256
+ *   accumulates from +0 the points b + t, b + t + 256, b + t + 512, b + t + 768 in that order, skipping those past N - 1
+ *   (a thread with no point keeps +0). The 256 accumulators are summed lane-wise inside each wave of 64 consecutive threads
+ *   by six pairwise steps in which both partners take a + b: lanes i <-> 7 - i inside each group of 8, then xor 1, xor 2,
+ *   i <-> 15 - i inside each row of 16, rows 0|1 and 2|3 of 16 lanes, the two halves of 32; then the four waves as
+ *   ((w0 + w1) + w2) + w3. The chunk sums are added to +0 in ascending chunk order. No atomics.
+ *   ws: a caller-provided workspace of S * ceil(N / NOVA_SOFT_CLUSTER_CHUNK) * K * 4 floats (the chunk partials); its
+ *   contents after the call are unspecified.
+ *   scale == 0 (temperature = +inf) is legal: every a_ik = 1 / K. A cluster all of whose a_ik underflow to 0 gives
+ *   out = +0.0f and mass = 0. No infinity enters this arithmetic.
+ * nova_pointset_soft_cluster_bwd: from g [S, K, 3] = dLoss/dout and gm [S, K] = dLoss/dmass (gm == NULL means zero), the
+ *   forward's inputs, its out and its mass: gx [S, N, 3] and gc [S, K, 3] (float32; gc is PER CLOUD in both centre forms).
+ *   The temperature gets no gradient. d_k, e_k, L, r, a_ik are recomputed as above, bit for bit. Then
+ *     u_k   = 1 / (mass_k + 1e-8f)                       one rounded addition, one IEEE division per centre
+ *     t_j   = x_i[j] - out_k[j]
+ *     dot   = fmaf(g_k[2], t_2, fmaf(g_k[1], t_1, g_k[0] * t_0))
+ *     h_k   = fmaf(u_k, dot, gm_k)
+ *     hbar  = a_i0 * h_0, then hbar = fmaf(a_ik, h_k, hbar) for k = 1 .. K-1 in that order
+ *     kappa = scale * 0.693147180559945309f              (= 1 / temperature; scale == 0 gives exactly 0 through d)
+ *     f_ik  = (kappa * (a_ik * (hbar - h_k))) * rcp(d_k) rcp the hardware's v_rcp_f32 (1 ulp); f_ik = 0 where d_k == 0: the
+ *                                                        subgradient convention of nova_pointset_nearest_match_bwd and of
+ *                                                        torch.cdist's backward: a point on a centre gives no gradient
+ *                                                        through that distance and no NaN
+ *     e_j   = x_i[j] - c_k[j]
+ *     gx[s, i, j]: R = +0, then for k = 0 .. K-1 in that order R = fmaf(f_ik, e_j, fmaf(a_ik * u_k, g_k[j], R)), the product
+ *                  a_ik * u_k rounded once. Local to the point: one thread per point, no reduction.
+ *     gc[s, k, j] = sum_i of -f_ik * e_j, each step acc = fmaf(-f_ik, e_j, acc), in the forward's order of summation.
+ *   A NULL gx or gc means "not wanted" and the work that only serves it is skipped; they may not both be NULL.
+ *   ws: S * ceil(N / NOVA_SOFT_CLUSTER_CHUNK) * K * 3 floats, read and written only when gc is given.
+ *   An empty cluster (mass_k = 0) has u_k = 1e8 and every a_ik = 0: finite gradients.
+ * nova_pointset_soft_cluster_sum_clouds: gcs[k, j] = the sum of gc[s, k, j] added to +0 in ascending s = 0 .. S-1, one
+ *   thread per element: the gradient of shared centres, to be formed after every launch has written its part of gc, so it
+ *   does not depend on the launch split. NOVA_ERR_SHAPE for K outside its range; S <= 0 returns 0 (gcs is not written);
+ *   then NOVA_ERR_ARG for a null pointer and for gcs overlapping gc.
+ * Consequences: out, mass, gx and gc of a cloud depend on that cloud's inputs, N, K and scale alone: bitwise the same for
+ * every batch, launch split, position in the batch and run. The centres live in registers on rungs of 8, 16 and 32; a
+ * result does not depend on the rung beyond the sign of a zero. Where every a_ik is exactly 0 or 1 / K with K a power of
+ * two and the sums are exact in float32 (small integer coordinates; scale == 0, or a temperature far below the gaps of the
+ * distances), out is the correctly rounded quotient of the exact sums.
+ * Limits: 1 <= N <= NOVA_SOFT_CLUSTER_MAX_POINTS; 1 <= K <= NOVA_SOFT_CLUSTER_MAX_K; at most 65535 clouds per call.
+ * Errors of the forward and the backward, in this order, before any device work: NOVA_ERR_SHAPE for N outside its range,
+ * for K outside its range, for S > 65535; NOVA_ERR_ARG for scale negative, NaN or infinite. S <= 0 returns 0 after these.
+ * Then NOVA_ERR_ARG for a null x, c, out, mass or ws (forward), a null x, c, out, mass or g (backward); backward only:
+ * NOVA_ERR_ARG for gx and gc both NULL, then for gc given with a null ws; last, NOVA_ERR_ARG when an output (out, mass, ws;
+ * gx, gc, ws) overlaps an input or another output.
+ * Added without a version bump (the number is pinned by the tests of three earlier entries; a library without the new
+ * symbols fails to bind, loudly). */
+#define NOVA_SOFT_CLUSTER_MAX_POINTS 65536
+#define NOVA_SOFT_CLUSTER_MAX_K 32
+#define NOVA_SOFT_CLUSTER_CHUNK 1024
+int nova_pointset_soft_cluster(const float* x, const float* c, float* out, float* mass, float* ws, int S, int N, int K,
+                               int shared_centers, float scale, void* stream);
+int nova_pointset_soft_cluster_bwd(const float* x, const float* c, const float* out, const float* mass, const float* g,
+                                   const float* gm, float* gx, float* gc, float* ws, int S, int N, int K, int shared_centers,
+                                   float scale, void* stream);
+int nova_pointset_soft_cluster_sum_clouds(const float* gc, float* gcs, int S, int K, void* stream);
+
 /* Nearest match with indices, and its backward: the primitive under the Chamfer-type training losses of the reference,
  * robust_chamfer_distance on distChamfer (train_newloss.py:316-349) and the edge-consistency term (train_newloss.py:449-457:
  * torch.cdist(subset1, subset2).min(dim=1), mean), which in PyTorch keep a [B, N, M] cdist matrix alive for the backward.

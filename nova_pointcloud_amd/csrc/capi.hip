@@ -528,6 +528,20 @@ int nova_pointset_kernel_interpolate_bwd(const float* q, const float* p, const f
   return pointset_kernel_interpolate_bwd(q, p, v, out, m, l, g, gq, gp, gv, S, T, N, C, scale, (hipStream_t)stream);
 }
 
+int nova_pointset_soft_cluster(const float* x, const float* c, float* out, float* mass, float* ws, int S, int N, int K, int shared_centers,
+                               float scale, void* stream) {
+  return pointset_soft_cluster(x, c, out, mass, ws, S, N, K, shared_centers, scale, (hipStream_t)stream);
+}
+
+int nova_pointset_soft_cluster_bwd(const float* x, const float* c, const float* out, const float* mass, const float* g, const float* gm,
+                                   float* gx, float* gc, float* ws, int S, int N, int K, int shared_centers, float scale, void* stream) {
+  return pointset_soft_cluster_bwd(x, c, out, mass, g, gm, gx, gc, ws, S, N, K, shared_centers, scale, (hipStream_t)stream);
+}
+
+int nova_pointset_soft_cluster_sum_clouds(const float* gc, float* gcs, int S, int K, void* stream) {
+  return pointset_soft_cluster_sum_clouds(gc, gcs, S, K, (hipStream_t)stream);
+}
+
 long long nova_pointset_assignment_state_bytes(int n) { return (long long)pointset_assignment_state_bytes(n); }
 
 int nova_pointset_assignment(const float* x, const float* y, int* col_of_row, float* cost, void* state, int B, int n, float clamp_lo,

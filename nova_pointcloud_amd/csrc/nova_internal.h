@@ -235,6 +235,12 @@ int pointset_kernel_interpolate_stats(const float* q, const float* p, const floa
 // ---- interp_bwd.hip (its backward: gradients of the queries, the source points and the values, no [T, N] array, no atomics)
 int pointset_kernel_interpolate_bwd(const float* q, const float* p, const float* v, const float* out, const float* m, const float* l,
                                     const float* g, float* gq, float* gp, float* gv, int S, int T, int N, int C, float scale, hipStream_t st);
+// ---- soft_cluster.hip (soft cluster pooling and its backward; 1 .. NOVA_SOFT_CLUSTER_MAX_POINTS points, 1 .. NOVA_SOFT_CLUSTER_MAX_K centres)
+int pointset_soft_cluster(const float* x, const float* c, float* out, float* mass, float* ws, int S, int N, int K, int shared_centers,
+                          float scale, hipStream_t st);
+int pointset_soft_cluster_bwd(const float* x, const float* c, const float* out, const float* mass, const float* g, const float* gm,
+                              float* gx, float* gc, float* ws, int S, int N, int K, int shared_centers, float scale, hipStream_t st);
+int pointset_soft_cluster_sum_clouds(const float* gc, float* gcs, int S, int K, hipStream_t st);
 // ---- assign.hip (optimal assignment of two clouds by a batched integer auction; point counts 1 .. NOVA_ASSIGN_MAX_POINTS)
 size_t pointset_assignment_state_bytes(int n);
 int pointset_assignment(const float* x, const float* y, int* col, float* cost, void* state, int B, int n, float lo, float hi,
