@@ -14,7 +14,8 @@ centres included (the per-cloud gradients are summed in ascending cloud order by
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import hip, metrics
+from . import hip
+from ._pointset import _at, _clouds_per_launch, _interp_scale, _launches, _launching
 
 SOFT_CLUSTER_MAX_POINTS = 65536  # == NOVA_SOFT_CLUSTER_MAX_POINTS of include/nova_hip.h
 SOFT_CLUSTER_MAX_K = 32  # == NOVA_SOFT_CLUSTER_MAX_K
@@ -70,12 +71,10 @@ class _SoftCluster(torch.autograd.Function):
         out = torch.empty(S, K, 3, dtype=torch.float32, device=x.device)
         mass = torch.empty(S, K, dtype=torch.float32, device=x.device)
         ws = torch.empty(min(S, per) * _chunks(N) * K * 4, dtype=torch.float32, device=x.device)  # one launch's chunk partials
-        with torch.cuda.device(x.device):
-            stream = hip.stream_ptr()
-            for s0, s1 in metrics._launches(S, per):
-                hip.call("nova_pointset_soft_cluster", x[s0].data_ptr(), c.data_ptr() if shared else c[s0].data_ptr(), out[s0].data_ptr(),
-                         mass[s0].data_ptr(), ws.data_ptr(), s1 - s0, N, K, 1 if shared else 0, scale, stream)
-                stats["forward_launches"] += 1
+        for stream, s0, count in _launching(x.device, S, per):
+            hip.call("nova_pointset_soft_cluster", _at(x, s0), c.data_ptr() if shared else _at(c, s0), _at(out, s0), _at(mass, s0),
+                     ws.data_ptr(), count, N, K, 1 if shared else 0, scale, stream)
+            stats["forward_launches"] += 1
         ctx.save_for_backward(x, c, out, mass)  # [S, N, 3], [K, 3] or [S, K, 3], [S, K, 3], [S, K]: nothing of size N K
         ctx.scale, ctx.per = scale, per
         ctx.set_materialize_grads(False)
@@ -96,13 +95,13 @@ class _SoftCluster(torch.autograd.Function):
         gx = torch.empty_like(x) if want_x else None
         gc = torch.empty(S, K, 3, dtype=torch.float32, device=x.device) if want_c else None  # per cloud in both centre forms
         ws = torch.empty(min(S, per) * _chunks(N) * K * 3, dtype=torch.float32, device=x.device) if want_c else None
-        at = lambda t, s0: t[s0].data_ptr() if t is not None else None
+        # written out, not _launching: the sum over the clouds follows the loop on the same device and stream
         with torch.cuda.device(x.device):
             stream = hip.stream_ptr()
-            for s0, s1 in metrics._launches(S, per):
-                hip.call("nova_pointset_soft_cluster_bwd", x[s0].data_ptr(), c.data_ptr() if shared else c[s0].data_ptr(), out[s0].data_ptr(),
-                         mass[s0].data_ptr(), g[s0].data_ptr(), at(gm, s0), at(gx, s0), at(gc, s0), ws.data_ptr() if want_c else None,
-                         s1 - s0, N, K, 1 if shared else 0, scale, stream)
+            for s0, count in _launches(S, per):
+                hip.call("nova_pointset_soft_cluster_bwd", _at(x, s0), c.data_ptr() if shared else _at(c, s0), _at(out, s0), _at(mass, s0),
+                         _at(g, s0), _at(gm, s0), _at(gx, s0), _at(gc, s0), ws.data_ptr() if want_c else None, count, N, K, 1 if shared else 0,
+                         scale, stream)
                 stats["point_grad_launches"] += 1 if want_x else 0
                 stats["center_grad_launches"] += 1 if want_c else 0
             if want_c and shared:  # after every launch has written its clouds: ascending cloud order, whatever the split
@@ -135,15 +134,12 @@ def soft_cluster_pool(points, centers, temperature=1.0, return_mass=False, max_c
     ValueError, in this order: types, dtypes, shapes, cloud counts, point and centre counts, devices, temperature,
     max_clouds_per_launch. NovaHipError for CPU tensors."""
     _pool_arguments(points, centers)
-    scale = metrics._interp_scale(temperature)
-    if max_clouds_per_launch is not None:
-        metrics._at_least_one(max_clouds_per_launch, "max_clouds_per_launch")
+    scale = _interp_scale(temperature)
+    per = _clouds_per_launch(max_clouds_per_launch, _default_clouds_per_launch(points.shape[1], centers.shape[-2]), _MAX_CLOUDS_PER_CALL)
     for t, name in ((points, "points"), (centers, "centers")):
         if not t.is_cuda:
             raise hip.NovaHipError(f"{name}: the soft cluster pooling runs on the GPU (got a CPU tensor)")
     xs = points.float().contiguous()
     cs = centers.float().contiguous()
-    N, K = xs.shape[1], cs.shape[-2]
-    per = _default_clouds_per_launch(N, K) if max_clouds_per_launch is None else min(max_clouds_per_launch, _MAX_CLOUDS_PER_CALL)
     out, mass = _SoftCluster.apply(xs, cs, scale, per)
     return (out, mass) if return_mass else out

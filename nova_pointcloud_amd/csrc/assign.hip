@@ -353,10 +353,17 @@ static void assign_launch(const float* x, const float* y, int* col, float* cost,
                      lo, hi, use_clamp, rounds, restart, all_done);
 }
 
-size_t pointset_assignment_state_bytes(int n) { return n >= 1 && n <= ASSIGN_MAX_N ? assign_state_bytes(n) : 0; }
+}  // namespace nova
 
-int pointset_assignment(const float* x, const float* y, int* col, float* cost, void* state, int B, int n, float lo, float hi,
-                        int use_clamp, int rounds, int restart, int* all_done, hipStream_t st) {
+using namespace nova;
+
+extern "C" {
+
+long long nova_pointset_assignment_state_bytes(int n) { return n >= 1 && n <= ASSIGN_MAX_N ? (long long)assign_state_bytes(n) : 0; }
+
+int nova_pointset_assignment(const float* x, const float* y, int* col, float* cost, void* state, int B, int n, float lo, float hi,
+                             int use_clamp, int rounds, int restart, int* all_done, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
   if (n < 1 || n > ASSIGN_MAX_N)
     return set_error(NOVA_ERR_ARG, "pointset_assignment: n %d outside 1 .. %d (NOVA_ASSIGN_MAX_POINTS)", n, ASSIGN_MAX_N);
   if (rounds < 1) return set_error(NOVA_ERR_ARG, "pointset_assignment: rounds %d < 1", rounds);
@@ -379,7 +386,8 @@ int pointset_assignment(const float* x, const float* y, int* col, float* cost, v
   return check_launch("pointset_assignment");
 }
 
-int pointset_assignment_rounds(const void* state, int* rounds_used, int B, int n, hipStream_t st) {
+int nova_pointset_assignment_rounds(const void* state, int* rounds_used, int B, int n, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
   if (n < 1 || n > ASSIGN_MAX_N)
     return set_error(NOVA_ERR_ARG, "pointset_assignment_rounds: n %d outside 1 .. %d (NOVA_ASSIGN_MAX_POINTS)", n, ASSIGN_MAX_N);
   if (B <= 0) return 0;
@@ -389,4 +397,4 @@ int pointset_assignment_rounds(const void* state, int* rounds_used, int B, int n
   return check_launch("pointset_assignment_rounds");
 }
 
-}  // namespace nova
+}  // extern "C"

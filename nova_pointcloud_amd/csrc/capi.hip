@@ -1,5 +1,6 @@
-// C ABI of libnova_hip.so (include/nova_hip.h): the error and profiling records, the single-kernel wrappers with their argument checks and the ViT
-// block stacks. The denoising loop, its hipGraph cache and the nova_debug_*_graphs entries are denoise.hip. Both check with nova_internal.h's macros.
+// C ABI of libnova_hip.so (include/nova_hip.h): the error and profiling records, the single-kernel wrappers of the model's kernels with their
+// argument checks and the ViT block stacks. The denoising loop, its hipGraph cache and the nova_debug_*_graphs entries are denoise.hip; the
+// nova_pointset_* entry points are defined in their kernel files (pointset.hip .. assign.hip). All check with nova_internal.h's macros.
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -422,136 +423,6 @@ int nova_vit_blocks_forward_kv(const nova_vit_block* blocks, int nblocks, void* 
                cache_len, L, cache_cap);
   return vit_blocks(blocks, nblocks, x, S, L, D, heads, hidden, rope, rope_batch, ws_qkv, ws_a, ws_b, ws_h, kv_cache, cache_cap,
                     cache_len, dtype, (hipStream_t)stream);
-}
-
-int nova_pointset_nn_dist(const float* x, const float* y, float* d, int B, int N, int M, float clamp_lo, float clamp_hi,
-                          int unit_norm, void* stream) {
-  NOVA_REQUIRE(B * (long)N == 0 || (x && y && d), NOVA_ERR_ARG, "pointset_nn_dist: null pointer");
-  NOVA_REQUIRE(clamp_lo <= clamp_hi, NOVA_ERR_ARG, "pointset_nn_dist: empty clamp range");
-  return pointset_nn_dist(x, y, d, B, N, M, clamp_lo, clamp_hi, unit_norm, (hipStream_t)stream);
-}
-
-int nova_pointset_pairwise_dist(const float* x, const float* y, float* D, int B, int N, int M, float clamp_lo, float clamp_hi,
-                                void* stream) {
-  NOVA_REQUIRE(B * (long)N * M == 0 || (x && y && D), NOVA_ERR_ARG, "pointset_pairwise_dist: null pointer");
-  NOVA_REQUIRE(clamp_lo <= clamp_hi, NOVA_ERR_ARG, "pointset_pairwise_dist: empty clamp range");
-  return pointset_pairwise_dist(x, y, D, B, N, M, clamp_lo, clamp_hi, (hipStream_t)stream);
-}
-
-int nova_pointset_nearest_match(const float* x, const float* y, float* d, int* idx, int B, int N, int M, float clamp_lo,
-                                float clamp_hi, int unit_norm, void* stream) {
-  NOVA_REQUIRE(B <= 0 || N <= 0 || (x && y && d && idx),NOVA_ERR_ARG, "pointset_nearest_match: null pointer");
-  NOVA_REQUIRE(clamp_lo <= clamp_hi, NOVA_ERR_ARG, "pointset_nearest_match: empty clamp range");
-  return pointset_nearest_match(x, y, d, idx, B, N, M, clamp_lo, clamp_hi, unit_norm, (hipStream_t)stream);
-}
-
-int nova_pointset_nearest_match_bwd(const float* x, const float* y, const int* idx, const float* g, float* gx, float* gy, int B,
-                                    int N, int M, float clamp_lo, float clamp_hi, int unit_norm, void* stream) {
-  NOVA_REQUIRE(B <= 0 || N <= 0 || (x && y && idx && g && gx && gy), NOVA_ERR_ARG, "pointset_nearest_match_bwd: null pointer");
-  NOVA_REQUIRE(clamp_lo <= clamp_hi, NOVA_ERR_ARG, "pointset_nearest_match_bwd: empty clamp range");
-  return pointset_nearest_match_bwd(x, y, idx, g, gx, gy, B, N, M, clamp_lo, clamp_hi, unit_norm, (hipStream_t)stream);
-}
-
-int nova_pointset_matched_dist(const float* x, const float* y, const int* idx, float* d, int B, int n, float clamp_lo, float clamp_hi,
-                               float floor, void* stream) {
-  NOVA_REQUIRE(B <= 0 || n <= 0 || (x && y && idx && d), NOVA_ERR_ARG, "pointset_matched_dist: null pointer");
-  NOVA_REQUIRE(clamp_lo <= clamp_hi, NOVA_ERR_ARG, "pointset_matched_dist: empty clamp range");
-  NOVA_REQUIRE(floor >= 0.f, NOVA_ERR_ARG, "pointset_matched_dist: floor must be >= 0");
-  return pointset_matched_dist(x, y, idx, d, B, n, clamp_lo, clamp_hi, floor, (hipStream_t)stream);
-}
-
-int nova_pointset_matched_dist_bwd(const float* x, const float* y, const int* idx, const int* inv, const float* g, float* gx, float* gy,
-                                   int B, int n, float clamp_lo, float clamp_hi, float floor, void* stream) {
-  NOVA_REQUIRE(B <= 0 || n <= 0 || (x && y && idx && inv && g && gx && gy), NOVA_ERR_ARG, "pointset_matched_dist_bwd: null pointer");
-  NOVA_REQUIRE(clamp_lo <= clamp_hi, NOVA_ERR_ARG, "pointset_matched_dist_bwd: empty clamp range");
-  NOVA_REQUIRE(floor >= 0.f, NOVA_ERR_ARG, "pointset_matched_dist_bwd: floor must be >= 0");
-  return pointset_matched_dist_bwd(x, y, idx, inv, g, gx, gy, B, n, clamp_lo, clamp_hi, floor, (hipStream_t)stream);
-}
-
-int nova_pointset_chamfer_matrix(const float* x, const float* y, float* cd, int A, int B, int N, int M, int ldc, int symmetric,
-                                 void* stream) {
-  NOVA_REQUIRE(A <= 0 || B <= 0 || (x && y && cd), NOVA_ERR_ARG, "pointset_chamfer_matrix: null pointer");
-  NOVA_REQUIRE(ldc >= B, NOVA_ERR_ARG, "pointset_chamfer_matrix: ldc %d < B %d", ldc, B);
-  NOVA_REQUIRE(!symmetric || (x == y && A == B && N == M), NOVA_ERR_ARG,
-               "pointset_chamfer_matrix: symmetric mode needs x == y, A == B and N == M");
-  return pointset_chamfer_matrix(x, y, cd, A, B, N, M, ldc, symmetric, (hipStream_t)stream);
-}
-
-int nova_pointset_emd_matrix(const float* x, const float* y, float* emd, int A, int B, int N, int ldc, void* stream) {
-  NOVA_REQUIRE(A <= 0 || B <= 0 || (x && y && emd), NOVA_ERR_ARG, "pointset_emd_matrix: null pointer");
-  NOVA_REQUIRE(ldc >= B, NOVA_ERR_ARG, "pointset_emd_matrix: ldc %d < B %d", ldc, B);
-  NOVA_REQUIRE(N >= 1 && N <= NOVA_EMD_MAX_POINTS, NOVA_ERR_ARG,
-               "pointset_emd_matrix: N %d outside 1 .. %d (the maximum point count NOVA_EMD_MAX_POINTS)", N, NOVA_EMD_MAX_POINTS);
-  return pointset_emd_matrix(x, y, emd, A, B, N, ldc, (hipStream_t)stream);
-}
-
-int nova_pointset_occupancy_grid(const float* x, long long* counters, long long* bernoulli, int* node, long long* outside, int S,
-                                 int N, int R, int in_sphere, int workgroups, void* stream) {
-  return pointset_occupancy_grid(x, counters, bernoulli, node, outside, S, N, R, in_sphere, workgroups, (hipStream_t)stream);
-}
-
-int nova_pointset_farthest_point_sample(const float* x, const int* start, int* idx, float* dist, int S, int N, int n, void* stream) {
-  return pointset_farthest_point_sample(x, start, idx, dist, S, N, n, (hipStream_t)stream);
-}
-
-int nova_pointset_knn(const float* x, const float* y, int* idx, float* d2, int S, int N, int M, int k, int exclude_self, void* stream) {
-  return pointset_knn(x, y, idx, d2, S, N, M, k, exclude_self, (hipStream_t)stream);
-}
-
-int nova_pointset_neighbor_aggregate(const float* f, const int* idx, const float* w, float* out, int S, int N, int M, int k, int C,
-                                     void* stream) {
-  return pointset_neighbor_aggregate(f, idx, w, out, S, N, M, k, C, (hipStream_t)stream);
-}
-
-int nova_pointset_neighbor_inverse(const int* idx, int* offsets, int* edges, int S, int N, int M, int k, void* stream) {
-  return pointset_neighbor_inverse(idx, offsets, edges, S, N, M, k, (hipStream_t)stream);
-}
-
-int nova_pointset_neighbor_aggregate_bwd(const float* f, const int* idx, const float* w, const float* g, const int* offsets,
-                                         const int* edges, float* gf, float* gw, int S, int N, int M, int k, int C, void* stream) {
-  return pointset_neighbor_aggregate_bwd(f, idx, w, g, offsets, edges, gf, gw, S, N, M, k, C, (hipStream_t)stream);
-}
-
-int nova_pointset_kernel_interpolate(const float* q, const float* p, const float* v, float* out, int S, int T, int N, int C, float scale,
-                                     void* stream) {
-  return pointset_kernel_interpolate(q, p, v, out, S, T, N, C, scale, (hipStream_t)stream);
-}
-
-int nova_pointset_kernel_interpolate_stats(const float* q, const float* p, const float* v, float* out, float* m, float* l, int S, int T,
-                                           int N, int C, float scale, void* stream) {
-  return pointset_kernel_interpolate_stats(q, p, v, out, m, l, S, T, N, C, scale, (hipStream_t)stream);
-}
-
-int nova_pointset_kernel_interpolate_bwd(const float* q, const float* p, const float* v, const float* out, const float* m, const float* l,
-                                         const float* g, float* gq, float* gp, float* gv, int S, int T, int N, int C, float scale,
-                                         void* stream) {
-  return pointset_kernel_interpolate_bwd(q, p, v, out, m, l, g, gq, gp, gv, S, T, N, C, scale, (hipStream_t)stream);
-}
-
-int nova_pointset_soft_cluster(const float* x, const float* c, float* out, float* mass, float* ws, int S, int N, int K, int shared_centers,
-                               float scale, void* stream) {
-  return pointset_soft_cluster(x, c, out, mass, ws, S, N, K, shared_centers, scale, (hipStream_t)stream);
-}
-
-int nova_pointset_soft_cluster_bwd(const float* x, const float* c, const float* out, const float* mass, const float* g, const float* gm,
-                                   float* gx, float* gc, float* ws, int S, int N, int K, int shared_centers, float scale, void* stream) {
-  return pointset_soft_cluster_bwd(x, c, out, mass, g, gm, gx, gc, ws, S, N, K, shared_centers, scale, (hipStream_t)stream);
-}
-
-int nova_pointset_soft_cluster_sum_clouds(const float* gc, float* gcs, int S, int K, void* stream) {
-  return pointset_soft_cluster_sum_clouds(gc, gcs, S, K, (hipStream_t)stream);
-}
-
-long long nova_pointset_assignment_state_bytes(int n) { return (long long)pointset_assignment_state_bytes(n); }
-
-int nova_pointset_assignment(const float* x, const float* y, int* col_of_row, float* cost, void* state, int B, int n, float clamp_lo,
-                             float clamp_hi, int use_clamp, int rounds, int restart, int* all_done, void* stream) {
-  return pointset_assignment(x, y, col_of_row, cost, state, B, n, clamp_lo, clamp_hi, use_clamp, rounds, restart, all_done,
-                             (hipStream_t)stream);
-}
-
-int nova_pointset_assignment_rounds(const void* state, int* rounds_used, int B, int n, void* stream) {
-  return pointset_assignment_rounds(state, rounds_used, B, n, (hipStream_t)stream);
 }
 
 int nova_modulate_rows(const void* x, const void* mod, void* out, long rows, int D, int dtype, void* stream) {

@@ -143,8 +143,19 @@ __global__ __launch_bounds__(CM_THREADS) void chamfer_matrix_kernel(const float*
   }
 }
 
-int pointset_chamfer_matrix(const float* x, const float* y, float* cd, int A, int B, int N, int M, int ldc, int symmetric,
-                            hipStream_t st) {
+}  // namespace nova
+
+using namespace nova;
+
+extern "C" {
+
+int nova_pointset_chamfer_matrix(const float* x, const float* y, float* cd, int A, int B, int N, int M, int ldc, int symmetric,
+                                 void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  NOVA_REQUIRE(A <= 0 || B <= 0 || (x && y && cd), NOVA_ERR_ARG, "pointset_chamfer_matrix: null pointer");
+  NOVA_REQUIRE(ldc >= B, NOVA_ERR_ARG, "pointset_chamfer_matrix: ldc %d < B %d", ldc, B);
+  NOVA_REQUIRE(!symmetric || (x == y && A == B && N == M), NOVA_ERR_ARG,
+               "pointset_chamfer_matrix: symmetric mode needs x == y, A == B and N == M");
   if (A <= 0 || B <= 0) return 0;
   if (N <= 0 || M <= 0) return set_error(NOVA_ERR_SHAPE, "pointset_chamfer_matrix: empty cloud (N %d, M %d)", N, M);
   const long pairs = symmetric ? (long)A * (A + 1) / 2 : (long)A * B;
@@ -155,4 +166,4 @@ int pointset_chamfer_matrix(const float* x, const float* y, float* cd, int A, in
   return check_launch("pointset_chamfer_matrix");
 }
 
-}  // namespace nova
+}  // extern "C"

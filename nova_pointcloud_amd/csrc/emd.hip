@@ -174,10 +174,19 @@ static void emd_launch(const float* x, const float* y, float* emd, long pairs, i
   hipLaunchKernelGGL((emd_matrix_kernel<T, R>), dim3((unsigned)pairs), dim3(T), 0, st, x, y, emd, B, N, (long)ldc);
 }
 
-int pointset_emd_matrix(const float* x, const float* y, float* emd, int A, int B, int N, int ldc, hipStream_t st) {
+}  // namespace nova
+
+using namespace nova;
+
+extern "C" {
+
+int nova_pointset_emd_matrix(const float* x, const float* y, float* emd, int A, int B, int N, int ldc, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  NOVA_REQUIRE(A <= 0 || B <= 0 || (x && y && emd), NOVA_ERR_ARG, "pointset_emd_matrix: null pointer");
+  NOVA_REQUIRE(ldc >= B, NOVA_ERR_ARG, "pointset_emd_matrix: ldc %d < B %d", ldc, B);
+  NOVA_REQUIRE(N >= 1 && N <= EMD_MAX_N, NOVA_ERR_ARG,
+               "pointset_emd_matrix: N %d outside 1 .. %d (the maximum point count NOVA_EMD_MAX_POINTS)", N, EMD_MAX_N);
   if (A <= 0 || B <= 0) return 0;
-  if (N < 1 || N > EMD_MAX_N)
-    return set_error(NOVA_ERR_ARG, "pointset_emd_matrix: N %d outside 1 .. %d (the maximum point count)", N, EMD_MAX_N);
   const long pairs = (long)A * B;
   if (pairs > 0x7fffffffL)
     return set_error(NOVA_ERR_SHAPE, "pointset_emd_matrix: %ld cloud pairs in one launch; split the pair grid", pairs);
@@ -194,4 +203,4 @@ int pointset_emd_matrix(const float* x, const float* y, float* emd, int A, int B
   return check_launch("pointset_emd_matrix");
 }
 
-}  // namespace nova
+}  // extern "C"

@@ -190,7 +190,14 @@ static void fps_launch(const float* x, const int* start, int* idx, float* dist, 
   hipLaunchKernelGGL((fps_kernel<P, T>), dim3((unsigned)S), dim3(T), 0, st, x, start, idx, dist, N, n);
 }
 
-int pointset_farthest_point_sample(const float* x, const int* start, int* idx, float* dist, int S, int N, int n, hipStream_t st) {
+}  // namespace nova
+
+using namespace nova;
+
+extern "C" {
+
+int nova_pointset_farthest_point_sample(const float* x, const int* start, int* idx, float* dist, int S, int N, int n, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
   if (N < 1 || N > FPS_MAX_N)
     return set_error(NOVA_ERR_SHAPE, "pointset_farthest_point_sample: N %d outside 1 .. %d (NOVA_FPS_MAX_POINTS)", N, FPS_MAX_N);
   if (n < 1 || n > N) return set_error(NOVA_ERR_ARG, "pointset_farthest_point_sample: n %d outside 1 .. N = %d", n, N);
@@ -211,4 +218,4 @@ int pointset_farthest_point_sample(const float* x, const int* start, int* idx, f
   return check_launch("pointset_farthest_point_sample");
 }
 
-}  // namespace nova
+}  // extern "C"

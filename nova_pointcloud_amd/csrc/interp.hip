@@ -202,8 +202,15 @@ static int interp_launch(const char* who, const float* q, const float* p, const 
   return check_launch(who);
 }
 
-int pointset_kernel_interpolate(const float* q, const float* p, const float* v, float* out, int S, int T, int N, int C, float scale,
-                                hipStream_t st) {
+}  // namespace nova
+
+using namespace nova;
+
+extern "C" {
+
+int nova_pointset_kernel_interpolate(const float* q, const float* p, const float* v, float* out, int S, int T, int N, int C, float scale,
+                                     void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
   const char* who = "pointset_kernel_interpolate";
   if (const int rc = interp_check(who, q, p, v, out, S, T, N, C, scale)) return rc;
   if (S <= 0) return 0;
@@ -212,8 +219,9 @@ int pointset_kernel_interpolate(const float* q, const float* p, const float* v, 
   return interp_launch<8, false>(who, q, p, v, out, nullptr, nullptr, S, T, N, C, scale, st);
 }
 
-int pointset_kernel_interpolate_stats(const float* q, const float* p, const float* v, float* out, float* m, float* l, int S, int T, int N,
-                                      int C, float scale, hipStream_t st) {
+int nova_pointset_kernel_interpolate_stats(const float* q, const float* p, const float* v, float* out, float* m, float* l, int S, int T, int N,
+                                           int C, float scale, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
   const char* who = "pointset_kernel_interpolate_stats";
   if (const int rc = interp_check(who, q, p, v, out, S, T, N, C, scale)) return rc;
   if (S > 0 && (!m || !l)) return set_error(NOVA_ERR_ARG, "%s: null pointer (m or l)", who);
@@ -223,4 +231,4 @@ int pointset_kernel_interpolate_stats(const float* q, const float* p, const floa
   return interp_launch<8, true>(who, q, p, v, out, m, l, S, T, N, C, scale, st);
 }
 
-}  // namespace nova
+}  // extern "C"

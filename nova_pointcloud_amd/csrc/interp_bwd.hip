@@ -310,8 +310,15 @@ static int interp_bwd_launch(const char* who, const float* q, const float* p, co
   return check_launch(who);
 }
 
-int pointset_kernel_interpolate_bwd(const float* q, const float* p, const float* v, const float* out, const float* m, const float* l,
-                                    const float* g, float* gq, float* gp, float* gv, int S, int T, int N, int C, float scale, hipStream_t st) {
+}  // namespace nova
+
+using namespace nova;
+
+extern "C" {
+
+int nova_pointset_kernel_interpolate_bwd(const float* q, const float* p, const float* v, const float* out, const float* m, const float* l,
+                                         const float* g, float* gq, float* gp, float* gv, int S, int T, int N, int C, float scale, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
   const char* who = "pointset_kernel_interpolate_bwd";
   if (const int rc = interp_check(who, q, p, v, out, S, T, N, C, scale)) return rc;
   if (S > 0) {
@@ -326,4 +333,4 @@ int pointset_kernel_interpolate_bwd(const float* q, const float* p, const float*
   return interp_bwd_launch<8>(who, q, p, v, out, m, l, g, gq, gp, gv, S, T, N, C, scale, st);
 }
 
-}  // namespace nova
+}  // extern "C"

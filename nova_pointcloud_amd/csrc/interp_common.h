@@ -37,8 +37,7 @@ inline int interp_check(const char* who, const float* q, const float* p, const f
   if (C < 1 || C > NOVA_INTERP_MAX_CHANNELS)
     return set_error(NOVA_ERR_SHAPE, "%s: C %d outside 1 .. %d (NOVA_INTERP_MAX_CHANNELS)", who, C, NOVA_INTERP_MAX_CHANNELS);
   if (!v && C != 3) return set_error(NOVA_ERR_ARG, "%s: v == NULL means the values are the source points and needs C == 3, got C %d", who, C);
-  if (!(scale >= 0.0f && scale <= 3.402823466e+38f))
-    return set_error(NOVA_ERR_ARG, "%s: scale %g must be finite and >= 0 (log2(e) / temperature)", who, (double)scale);
+  NOVA_TRY(check_scale(who, scale));
   if (S > 0 && (!q || !p || !out)) return set_error(NOVA_ERR_ARG, "%s: null pointer", who);
   return 0;
 }

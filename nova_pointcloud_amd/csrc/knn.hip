@@ -172,7 +172,14 @@ static int knn_launch(const float* x, const float* y, int* idx, float* d2, int S
   return check_launch("pointset_knn");
 }
 
-int pointset_knn(const float* x, const float* y, int* idx, float* d2, int S, int N, int M, int k, int exclude_self, hipStream_t st) {
+}  // namespace nova
+
+using namespace nova;
+
+extern "C" {
+
+int nova_pointset_knn(const float* x, const float* y, int* idx, float* d2, int S, int N, int M, int k, int exclude_self, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
   if (N < 1 || N > KNN_MAX_N || M < 1 || M > KNN_MAX_N)
     return set_error(NOVA_ERR_SHAPE, "pointset_knn: N %d or M %d outside 1 .. %d (NOVA_KNN_MAX_POINTS)", N, M, KNN_MAX_N);
   if (exclude_self && N != M) return set_error(NOVA_ERR_SHAPE, "pointset_knn: exclude_self needs N == M, got N %d and M %d", N, M);
@@ -190,4 +197,4 @@ int pointset_knn(const float* x, const float* y, int* idx, float* d2, int S, int
   return knn_launch<32>(x, y, idx, d2, S, N, M, k, exclude_self, st);
 }
 
-}  // namespace nova
+}  // extern "C"

@@ -92,16 +92,30 @@ __global__ __launch_bounds__(MD_T) void matched_dist_gy_kernel(const float* __re
   store_masked(gy + ((size_t)b * n + j) * 3, yb + (size_t)j * 3, lo, hi, -t0, -t1, -t2);
 }
 
-int pointset_matched_dist(const float* x, const float* y, const int* idx, float* d, int B, int n, float lo, float hi, float floor,
-                          hipStream_t st) {
+}  // namespace nova
+
+using namespace nova;
+
+extern "C" {
+
+int nova_pointset_matched_dist(const float* x, const float* y, const int* idx, float* d, int B, int n, float lo, float hi, float floor,
+                               void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  NOVA_REQUIRE(B <= 0 || n <= 0 || (x && y && idx && d), NOVA_ERR_ARG, "pointset_matched_dist: null pointer");
+  NOVA_REQUIRE(lo <= hi, NOVA_ERR_ARG, "pointset_matched_dist: empty clamp range");
+  NOVA_REQUIRE(floor >= 0.f, NOVA_ERR_ARG, "pointset_matched_dist: floor must be >= 0");
   if (B <= 0 || n <= 0) return 0;
   if (B > 65535) return set_error(NOVA_ERR_SHAPE, "pointset_matched_dist: batch %d too large", B);
   hipLaunchKernelGGL(matched_dist_kernel, dim3((n + MD_T - 1) / MD_T, B), dim3(MD_T), 0, st, x, y, idx, d, n, lo, hi, floor);
   return check_launch("pointset_matched_dist");
 }
 
-int pointset_matched_dist_bwd(const float* x, const float* y, const int* idx, const int* inv, const float* g, float* gx, float* gy, int B,
-                              int n, float lo, float hi, float floor, hipStream_t st) {
+int nova_pointset_matched_dist_bwd(const float* x, const float* y, const int* idx, const int* inv, const float* g, float* gx, float* gy, int B,
+                                   int n, float lo, float hi, float floor, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  NOVA_REQUIRE(B <= 0 || n <= 0 || (x && y && idx && inv && g && gx && gy), NOVA_ERR_ARG, "pointset_matched_dist_bwd: null pointer");
+  NOVA_REQUIRE(lo <= hi, NOVA_ERR_ARG, "pointset_matched_dist_bwd: empty clamp range");
+  NOVA_REQUIRE(floor >= 0.f, NOVA_ERR_ARG, "pointset_matched_dist_bwd: floor must be >= 0");
   if (B <= 0 || n <= 0) return 0;
   if (B > 65535) return set_error(NOVA_ERR_SHAPE, "pointset_matched_dist_bwd: batch %d too large", B);
   const dim3 grid((n + MD_T - 1) / MD_T, B);
@@ -110,4 +124,4 @@ int pointset_matched_dist_bwd(const float* x, const float* y, const int* idx, co
   return check_launch("pointset_matched_dist_bwd");
 }
 
-}  // namespace nova
+}  // extern "C"

@@ -174,8 +174,17 @@ __global__ __launch_bounds__(NM_T) void nearest_match_gy_kernel(const float* __r
   out[2] = r2;
 }
 
-int pointset_nearest_match(const float* x, const float* y, float* d, int* idx, int B, int N, int M, float lo, float hi, int unit,
-                           hipStream_t st) {
+}  // namespace nova
+
+using namespace nova;
+
+extern "C" {
+
+int nova_pointset_nearest_match(const float* x, const float* y, float* d, int* idx, int B, int N, int M, float lo, float hi, int unit,
+                                void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  NOVA_REQUIRE(B <= 0 || N <= 0 || (x && y && d && idx), NOVA_ERR_ARG, "pointset_nearest_match: null pointer");
+  NOVA_REQUIRE(lo <= hi, NOVA_ERR_ARG, "pointset_nearest_match: empty clamp range");
   if (B <= 0 || N <= 0) return 0;
   if (M <= 0) return set_error(NOVA_ERR_SHAPE, "pointset_nearest_match: empty target set");
   if (B > 65535) return set_error(NOVA_ERR_SHAPE, "pointset_nearest_match: batch %d too large", B);
@@ -183,8 +192,11 @@ int pointset_nearest_match(const float* x, const float* y, float* d, int* idx, i
   return check_launch("pointset_nearest_match");
 }
 
-int pointset_nearest_match_bwd(const float* x, const float* y, const int* idx, const float* g, float* gx, float* gy, int B, int N, int M,
-                               float lo, float hi, int unit, hipStream_t st) {
+int nova_pointset_nearest_match_bwd(const float* x, const float* y, const int* idx, const float* g, float* gx, float* gy, int B, int N, int M,
+                                    float lo, float hi, int unit, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  NOVA_REQUIRE(B <= 0 || N <= 0 || (x && y && idx && g && gx && gy), NOVA_ERR_ARG, "pointset_nearest_match_bwd: null pointer");
+  NOVA_REQUIRE(lo <= hi, NOVA_ERR_ARG, "pointset_nearest_match_bwd: empty clamp range");
   if (B <= 0 || N <= 0) return 0;
   if (M <= 0) return set_error(NOVA_ERR_SHAPE, "pointset_nearest_match_bwd: empty target set");
   if (B > 65535) return set_error(NOVA_ERR_SHAPE, "pointset_nearest_match_bwd: batch %d too large", B);
@@ -193,4 +205,4 @@ int pointset_nearest_match_bwd(const float* x, const float* y, const int* idx, c
   return check_launch("pointset_nearest_match_bwd");
 }
 
-}  // namespace nova
+}  // extern "C"

@@ -300,10 +300,6 @@ __global__ __launch_bounds__(NB_T) void neighbor_fill_kernel(const int* __restri
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
-static bool nb_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a && b && a0 < b0 + nb && b0 < a0 + na;
-}
 static bool nb_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // the checks the three entries share, in the order include/nova_hip.h states: N, M (and C), k, S
@@ -316,14 +312,21 @@ static int nb_shape(const char* who, int S, int N, int M, int k, int C) {
   return 0;
 }
 
-int pointset_neighbor_aggregate(const float* f, const int* idx, const float* w, float* out, int S, int N, int M, int k, int C,
-                                hipStream_t st) {
+}  // namespace nova
+
+using namespace nova;
+
+extern "C" {
+
+int nova_pointset_neighbor_aggregate(const float* f, const int* idx, const float* w, float* out, int S, int N, int M, int k, int C,
+                                     void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
   const char* who = "pointset_neighbor_aggregate";
   if (const int rc = nb_shape(who, S, N, M, k, C)) return rc;
   if (S <= 0) return 0;
   if (!f || !idx || !out) return set_error(NOVA_ERR_ARG, "%s: null pointer", who);
   const size_t nf = (size_t)S * M * C * 4, ni = (size_t)S * N * k * 4, no = (size_t)S * N * C * 4;
-  if (nb_overlap(out, no, f, nf) || nb_overlap(out, no, idx, ni) || nb_overlap(out, no, w, ni))
+  if (ranges_overlap(out, no, f, nf) || ranges_overlap(out, no, idx, ni) || ranges_overlap(out, no, w, ni))
     return set_error(NOVA_ERR_ARG, "%s: out overlaps an input", who);
   const dim3 grid((N + NB_WAVES - 1) / NB_WAVES, S), block(NB_T);
   const bool v4 = C % 4 == 0 && nb_aligned16(f) && nb_aligned16(out);
@@ -337,13 +340,14 @@ int pointset_neighbor_aggregate(const float* f, const int* idx, const float* w, 
   return check_launch(who);
 }
 
-int pointset_neighbor_inverse(const int* idx, int* offsets, int* edges, int S, int N, int M, int k, hipStream_t st) {
+int nova_pointset_neighbor_inverse(const int* idx, int* offsets, int* edges, int S, int N, int M, int k, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
   const char* who = "pointset_neighbor_inverse";
   if (const int rc = nb_shape(who, S, N, M, k, 1)) return rc;
   if (S <= 0) return 0;
   if (!idx || !offsets || !edges) return set_error(NOVA_ERR_ARG, "%s: null pointer", who);
   const size_t ni = (size_t)S * N * k * 4, noff = (size_t)S * (M + 1) * 4;
-  if (nb_overlap(offsets, noff, idx, ni) || nb_overlap(edges, ni, idx, ni) || nb_overlap(offsets, noff, edges, ni))
+  if (ranges_overlap(offsets, noff, idx, ni) || ranges_overlap(edges, ni, idx, ni) || ranges_overlap(offsets, noff, edges, ni))
     return set_error(NOVA_ERR_ARG, "%s: offsets or edges overlap idx or each other", who);
   const dim3 grid((M + NB_Q - 1) / NB_Q, S), block(NB_T);
   hipLaunchKernelGGL(neighbor_count_kernel, grid, block, 0, st, idx, offsets, N, M, k);
@@ -352,8 +356,9 @@ int pointset_neighbor_inverse(const int* idx, int* offsets, int* edges, int S, i
   return check_launch(who);
 }
 
-int pointset_neighbor_aggregate_bwd(const float* f, const int* idx, const float* w, const float* g, const int* offsets,
-                                    const int* edges, float* gf, float* gw, int S, int N, int M, int k, int C, hipStream_t st) {
+int nova_pointset_neighbor_aggregate_bwd(const float* f, const int* idx, const float* w, const float* g, const int* offsets,
+                                         const int* edges, float* gf, float* gw, int S, int N, int M, int k, int C, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
   const char* who = "pointset_neighbor_aggregate_bwd";
   if (const int rc = nb_shape(who, S, N, M, k, C)) return rc;
   if (S <= 0) return 0;
@@ -362,9 +367,9 @@ int pointset_neighbor_aggregate_bwd(const float* f, const int* idx, const float*
   if (!gf && !gw) return set_error(NOVA_ERR_ARG, "%s: gf and gw are both NULL", who);
   if (gf && (!offsets || !edges)) return set_error(NOVA_ERR_ARG, "%s: gf needs the inverse list (offsets, edges)", who);
   const size_t nf = (size_t)S * M * C * 4, ni = (size_t)S * N * k * 4, ng = (size_t)S * N * C * 4, noff = (size_t)S * (M + 1) * 4;
-  if (nb_overlap(gf, nf, f, nf) || nb_overlap(gf, nf, idx, ni) || nb_overlap(gf, nf, w, ni) || nb_overlap(gf, nf, g, ng) ||
-      nb_overlap(gf, nf, offsets, noff) || nb_overlap(gf, nf, edges, ni) || nb_overlap(gw, ni, f, nf) || nb_overlap(gw, ni, idx, ni) ||
-      nb_overlap(gw, ni, w, ni) || nb_overlap(gw, ni, g, ng) || nb_overlap(gw, ni, gf, nf))
+  if (ranges_overlap(gf, nf, f, nf) || ranges_overlap(gf, nf, idx, ni) || ranges_overlap(gf, nf, w, ni) || ranges_overlap(gf, nf, g, ng) ||
+      ranges_overlap(gf, nf, offsets, noff) || ranges_overlap(gf, nf, edges, ni) || ranges_overlap(gw, ni, f, nf) ||
+      ranges_overlap(gw, ni, idx, ni) || ranges_overlap(gw, ni, w, ni) || ranges_overlap(gw, ni, g, ng) || ranges_overlap(gw, ni, gf, nf))
     return set_error(NOVA_ERR_ARG, "%s: gf or gw overlaps an input or each other", who);
   const dim3 block(NB_T);
   if (gf) {
@@ -382,4 +387,4 @@ int pointset_neighbor_aggregate_bwd(const float* f, const int* idx, const float*
   return check_launch(who);
 }
 
-}  // namespace nova
+}  // extern "C"

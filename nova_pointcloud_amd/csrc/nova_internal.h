@@ -1,4 +1,5 @@
-// Internal declarations shared by the kernel translation units and the C ABI (capi.hip, denoise.hip).
+// Internal declarations shared by the kernel translation units and the C ABI (capi.hip, denoise.hip). The point-set files declare nothing
+// here: each defines its extern "C" entry points itself and takes only set_error, check_launch, NOVA_REQUIRE and NOVA_TRY from this header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -194,57 +195,5 @@ int renorm_step(float* x, const float* vhat, const float* cond, const float* ext
                 int B, int nP, int eP, const SamplerStep& sp, float renorm, int echo_only, hipStream_t st);
 int kv_append(const void* qkv, void* cache, int S, int Lq, int D, long cap, long base, int dtype, hipStream_t st);
 int modulate_rows(const void* x, const void* mod, void* out, long rows, int D, int dtype, hipStream_t st);
-
-
-// ---- pointset.hip (Chamfer / EMD distance work)
-int pointset_nn_dist(const float* x, const float* y, float* d, int B, int N, int M, float lo, float hi, int unit, hipStream_t st);
-int pointset_pairwise_dist(const float* x, const float* y, float* D, int B, int N, int M, float lo, float hi, hipStream_t st);
-// ---- nearest_match.hip (nearest match with indices and its backward: the Chamfer-type training losses)
-int pointset_nearest_match(const float* x, const float* y, float* d, int* idx, int B, int N, int M, float lo, float hi, int unit,
-                           hipStream_t st);
-int pointset_nearest_match_bwd(const float* x, const float* y, const int* idx, const float* g, float* gx, float* gy, int B, int N, int M,
-                               float lo, float hi, int unit, hipStream_t st);
-// ---- matched.hip (distance of matched pairs under a given permutation and its backward: the exact-assignment EMD training loss)
-int pointset_matched_dist(const float* x, const float* y, const int* idx, float* d, int B, int n, float lo, float hi, float floor,
-                          hipStream_t st);
-int pointset_matched_dist_bwd(const float* x, const float* y, const int* idx, const int* inv, const float* g, float* gx, float* gy, int B,
-                              int n, float lo, float hi, float floor, hipStream_t st);
-// ---- chamfer.hip (all-pairs Chamfer matrix for MMD / COV / 1-NNA)
-int pointset_chamfer_matrix(const float* x, const float* y, float* cd, int A, int B, int N, int M, int ldc, int symmetric,
-                            hipStream_t st);
-// ---- emd.hip (all-pairs approxmatch EMD matrix for MMD / COV / 1-NNA; point counts 1 .. EMD_MAX_N)
-int pointset_emd_matrix(const float* x, const float* y, float* emd, int A, int B, int N, int ldc, hipStream_t st);
-// ---- occupancy.hip (occupancy grid of a cloud set for the JSD metric; resolutions 2 .. NOVA_OCC_MAX_RES)
-int pointset_occupancy_grid(const float* x, long long* counters, long long* bernoulli, int* node, long long* outside, int S, int N,
-                            int R, int in_sphere, int workgroups, hipStream_t st);
-// ---- fps.hip (farthest point sampling of a cloud set; point counts 1 .. NOVA_FPS_MAX_POINTS)
-int pointset_farthest_point_sample(const float* x, const int* start, int* idx, float* dist, int S, int N, int n, hipStream_t st);
-// ---- knn.hip (exact k nearest neighbours of a cloud set; k 1 .. NOVA_KNN_MAX_K, point counts 1 .. NOVA_KNN_MAX_POINTS)
-int pointset_knn(const float* x, const float* y, int* idx, float* d2, int S, int N, int M, int k, int exclude_self, hipStream_t st);
-// ---- neighbor.hip (kNN neighbourhood feature aggregation, its inverse neighbour list and its backward; 1 .. NOVA_NEIGHBOR_MAX_CHANNELS channels)
-int pointset_neighbor_aggregate(const float* f, const int* idx, const float* w, float* out, int S, int N, int M, int k, int C,
-                                hipStream_t st);
-int pointset_neighbor_inverse(const int* idx, int* offsets, int* edges, int S, int N, int M, int k, hipStream_t st);
-int pointset_neighbor_aggregate_bwd(const float* f, const int* idx, const float* w, const float* g, const int* offsets,
-                                    const int* edges, float* gf, float* gw, int S, int N, int M, int k, int C, hipStream_t st);
-// ---- interp.hip (distance-weighted interpolation of values over a cloud set; point counts 1 .. NOVA_INTERP_MAX_POINTS, 1 .. NOVA_INTERP_MAX_CHANNELS channels)
-int pointset_kernel_interpolate(const float* q, const float* p, const float* v, float* out, int S, int T, int N, int C, float scale,
-                                hipStream_t st);
-int pointset_kernel_interpolate_stats(const float* q, const float* p, const float* v, float* out, float* m, float* l, int S, int T, int N,
-                                      int C, float scale, hipStream_t st);
-// ---- interp_bwd.hip (its backward: gradients of the queries, the source points and the values, no [T, N] array, no atomics)
-int pointset_kernel_interpolate_bwd(const float* q, const float* p, const float* v, const float* out, const float* m, const float* l,
-                                    const float* g, float* gq, float* gp, float* gv, int S, int T, int N, int C, float scale, hipStream_t st);
-// ---- soft_cluster.hip (soft cluster pooling and its backward; 1 .. NOVA_SOFT_CLUSTER_MAX_POINTS points, 1 .. NOVA_SOFT_CLUSTER_MAX_K centres)
-int pointset_soft_cluster(const float* x, const float* c, float* out, float* mass, float* ws, int S, int N, int K, int shared_centers,
-                          float scale, hipStream_t st);
-int pointset_soft_cluster_bwd(const float* x, const float* c, const float* out, const float* mass, const float* g, const float* gm,
-                              float* gx, float* gc, float* ws, int S, int N, int K, int shared_centers, float scale, hipStream_t st);
-int pointset_soft_cluster_sum_clouds(const float* gc, float* gcs, int S, int K, hipStream_t st);
-// ---- assign.hip (optimal assignment of two clouds by a batched integer auction; point counts 1 .. NOVA_ASSIGN_MAX_POINTS)
-size_t pointset_assignment_state_bytes(int n);
-int pointset_assignment(const float* x, const float* y, int* col, float* cost, void* state, int B, int n, float lo, float hi,
-                        int use_clamp, int rounds, int restart, int* all_done, hipStream_t st);
-int pointset_assignment_rounds(const void* state, int* rounds_used, int B, int n, hipStream_t st);
 
 }  // namespace nova

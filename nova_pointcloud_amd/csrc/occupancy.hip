@@ -173,8 +173,15 @@ __global__ __launch_bounds__(OCC_THREADS) void occupancy_grid_kernel(const float
   if (t == 0 && outside && s.outside) atomicAdd(outside, (unsigned long long)s.outside);
 }
 
-int pointset_occupancy_grid(const float* x, long long* counters, long long* bernoulli, int* node, long long* outside, int S, int N,
-                            int R, int in_sphere, int workgroups, hipStream_t st) {
+}  // namespace nova
+
+using namespace nova;
+
+extern "C" {
+
+int nova_pointset_occupancy_grid(const float* x, long long* counters, long long* bernoulli, int* node, long long* outside, int S, int N,
+                                 int R, int in_sphere, int workgroups, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
   if (N <= 0) return set_error(NOVA_ERR_SHAPE, "pointset_occupancy_grid: empty cloud (N %d)", N);
   if (N > OCC_MAX_POINTS)
     return set_error(NOVA_ERR_SHAPE, "pointset_occupancy_grid: N %d above %ld points per cloud", N, OCC_MAX_POINTS);
@@ -195,4 +202,4 @@ int pointset_occupancy_grid(const float* x, long long* counters, long long* bern
   return check_launch("pointset_occupancy_grid");
 }
 
-}  // namespace nova
+}  // extern "C"

@@ -65,7 +65,16 @@ __global__ __launch_bounds__(256) void pairwise_dist_kernel(const float* __restr
   }
 }
 
-int pointset_nn_dist(const float* x, const float* y, float* d, int B, int N, int M, float lo, float hi, int unit, hipStream_t st) {
+}  // namespace nova
+
+using namespace nova;
+
+extern "C" {
+
+int nova_pointset_nn_dist(const float* x, const float* y, float* d, int B, int N, int M, float lo, float hi, int unit, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  NOVA_REQUIRE(B * (long)N == 0 || (x && y && d), NOVA_ERR_ARG, "pointset_nn_dist: null pointer");
+  NOVA_REQUIRE(lo <= hi, NOVA_ERR_ARG, "pointset_nn_dist: empty clamp range");
   if (B <= 0 || N <= 0) return 0;
   if (M <= 0) return set_error(NOVA_ERR_SHAPE, "pointset_nn_dist: empty target set");
   if (B > 65535) return set_error(NOVA_ERR_SHAPE, "pointset_nn_dist: batch %d too large", B);
@@ -73,11 +82,14 @@ int pointset_nn_dist(const float* x, const float* y, float* d, int B, int N, int
   return check_launch("pointset_nn_dist");
 }
 
-int pointset_pairwise_dist(const float* x, const float* y, float* D, int B, int N, int M, float lo, float hi, hipStream_t st) {
+int nova_pointset_pairwise_dist(const float* x, const float* y, float* D, int B, int N, int M, float lo, float hi, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  NOVA_REQUIRE(B * (long)N * M == 0 || (x && y && D), NOVA_ERR_ARG, "pointset_pairwise_dist: null pointer");
+  NOVA_REQUIRE(lo <= hi, NOVA_ERR_ARG, "pointset_pairwise_dist: empty clamp range");
   if (B <= 0 || N <= 0 || M <= 0) return 0;
   if (B > 65535 || (N + 15) / 16 > 65535) return set_error(NOVA_ERR_SHAPE, "pointset_pairwise_dist: grid too large");
   hipLaunchKernelGGL(pairwise_dist_kernel, dim3((M + 255) / 256, (N + 15) / 16, B), dim3(256), 0, st, x, y, D, N, M, lo, hi);
   return check_launch("pointset_pairwise_dist");
 }
 
-}  // namespace nova
+}  // extern "C"

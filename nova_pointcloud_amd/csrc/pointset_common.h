@@ -1,8 +1,9 @@
 // Device helpers shared by the point-set kernels (pointset, chamfer, emd, occupancy, fps, assign, knn, interp): every result of
 // that family is bitwise the same for every batch and launch split, which rests on all of them computing one distance
-// expression and summing in one fixed order. Both are defined here once.
+// expression and summing in one fixed order. Both are defined here once. After them, the two host-side argument checks
+// that more than one entry point states in the same words.
 #pragma once
-#include "common.h"
+#include "nova_internal.h"
 
 namespace nova {
 
@@ -63,6 +64,22 @@ template <int WAVES> __device__ __forceinline__ float block_sum_fixed(float v, f
 #pragma unroll
   for (int w = 1; w < WAVES; ++w) total += red[w];
   return total;
+}
+
+// ---- host side: each point-set file defines its own extern "C" nova_pointset_* entry points after its kernels, with all of
+// their checks in one place (include/nova_hip.h is the contract). Only checks that are the same text everywhere live here.
+
+// do the byte ranges [a, a + na) and [b, b + nb) intersect? A NULL pointer overlaps nothing.
+inline bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a && b && a0 < b0 + nb && b0 < a0 + na;
+}
+
+// scale = log2(e) / temperature of the interpolation and the soft clusters: finite and >= 0 (NaN fails); 0 when it passes
+inline int check_scale(const char* who, float scale) {
+  if (!(scale >= 0.0f && scale <= 3.402823466e+38f))
+    return set_error(NOVA_ERR_ARG, "%s: scale %g must be finite and >= 0 (log2(e) / temperature)", who, (double)scale);
+  return 0;
 }
 
 }  // namespace nova

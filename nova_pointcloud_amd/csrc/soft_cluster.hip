@@ -263,45 +263,12 @@ __global__ __launch_bounds__(SC_T) void soft_cluster_sum_clouds_kernel(const flo
 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
-static bool sc_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return a && b && a0 < b0 + nb && b0 < a0 + na;
-}
-
 // the checks both entries share, in the order include/nova_hip.h states: N, K, S (shape), then scale (argument)
 static int sc_check(const char* who, int S, int N, int K, float scale) {
   if (N < 1 || N > SC_MAX_N) return set_error(NOVA_ERR_SHAPE, "%s: N %d outside 1 .. %d (NOVA_SOFT_CLUSTER_MAX_POINTS)", who, N, SC_MAX_N);
   if (K < 1 || K > SC_MAX_K) return set_error(NOVA_ERR_SHAPE, "%s: K %d outside 1 .. %d (NOVA_SOFT_CLUSTER_MAX_K)", who, K, SC_MAX_K);
   if (S > 65535) return set_error(NOVA_ERR_SHAPE, "%s: %d clouds exceed one launch (65535)", who, S);
-  if (!(scale >= 0.0f && scale <= 3.402823466e+38f))
-    return set_error(NOVA_ERR_ARG, "%s: scale %g must be finite and >= 0 (log2(e) / temperature)", who, (double)scale);
-  return 0;
-}
-
-int pointset_soft_cluster(const float* x, const float* c, float* out, float* mass, float* ws, int S, int N, int K, int shared_centers,
-                          float scale, hipStream_t st) {
-  const char* who = "pointset_soft_cluster";
-  if (const int rc = sc_check(who, S, N, K, scale)) return rc;
-  if (S <= 0) return 0;
-  if (!x || !c || !out || !mass || !ws) return set_error(NOVA_ERR_ARG, "%s: null pointer", who);
-  const int chunks = (N + SC_CHUNK - 1) / SC_CHUNK;
-  const size_t nx = (size_t)S * N * 12, nc = (size_t)(shared_centers ? 1 : S) * K * 12, no = (size_t)S * K * 12, nm = (size_t)S * K * 4,
-               nw = (size_t)S * chunks * K * 16;
-  const void* outs[3] = {out, mass, ws};
-  const size_t nouts[3] = {no, nm, nw};
-  for (int a = 0; a < 3; ++a) {
-    if (sc_overlap(outs[a], nouts[a], x, nx) || sc_overlap(outs[a], nouts[a], c, nc))
-      return set_error(NOVA_ERR_ARG, "%s: out, mass or ws overlaps an input", who);
-    for (int b = a + 1; b < 3; ++b)
-      if (sc_overlap(outs[a], nouts[a], outs[b], nouts[b])) return set_error(NOVA_ERR_ARG, "%s: out, mass and ws overlap each other", who);
-  }
-  const dim3 grid(chunks, S), block(SC_T);
-  const size_t cstride = shared_centers ? 0 : (size_t)K * 3;
-  if (K <= 8) hipLaunchKernelGGL((soft_cluster_fwd_kernel<8>), grid, block, 0, st, x, c, ws, N, K, cstride, scale);
-  else if (K <= 16) hipLaunchKernelGGL((soft_cluster_fwd_kernel<16>), grid, block, 0, st, x, c, ws, N, K, cstride, scale);
-  else hipLaunchKernelGGL((soft_cluster_fwd_kernel<32>), grid, block, 0, st, x, c, ws, N, K, cstride, scale);
-  hipLaunchKernelGGL(soft_cluster_merge_kernel, dim3((unsigned)(((size_t)S * K + SC_T - 1) / SC_T)), block, 0, st, ws, out, mass, S, K, chunks);
-  return check_launch(who);
+  return check_scale(who, scale);
 }
 
 template <int KR>
@@ -316,8 +283,42 @@ static void sc_bwd_launch(dim3 grid, hipStream_t st, const float* x, const float
     hipLaunchKernelGGL((soft_cluster_bwd_kernel<KR, false, true>), grid, block, 0, st, x, c, out, mass, g, gm, gx, ws, N, K, cstride, scale);
 }
 
-int pointset_soft_cluster_bwd(const float* x, const float* c, const float* out, const float* mass, const float* g, const float* gm,
-                              float* gx, float* gc, float* ws, int S, int N, int K, int shared_centers, float scale, hipStream_t st) {
+}  // namespace nova
+
+using namespace nova;
+
+extern "C" {
+
+int nova_pointset_soft_cluster(const float* x, const float* c, float* out, float* mass, float* ws, int S, int N, int K, int shared_centers,
+                               float scale, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
+  const char* who = "pointset_soft_cluster";
+  if (const int rc = sc_check(who, S, N, K, scale)) return rc;
+  if (S <= 0) return 0;
+  if (!x || !c || !out || !mass || !ws) return set_error(NOVA_ERR_ARG, "%s: null pointer", who);
+  const int chunks = (N + SC_CHUNK - 1) / SC_CHUNK;
+  const size_t nx = (size_t)S * N * 12, nc = (size_t)(shared_centers ? 1 : S) * K * 12, no = (size_t)S * K * 12, nm = (size_t)S * K * 4,
+               nw = (size_t)S * chunks * K * 16;
+  const void* outs[3] = {out, mass, ws};
+  const size_t nouts[3] = {no, nm, nw};
+  for (int a = 0; a < 3; ++a) {
+    if (ranges_overlap(outs[a], nouts[a], x, nx) || ranges_overlap(outs[a], nouts[a], c, nc))
+      return set_error(NOVA_ERR_ARG, "%s: out, mass or ws overlaps an input", who);
+    for (int b = a + 1; b < 3; ++b)
+      if (ranges_overlap(outs[a], nouts[a], outs[b], nouts[b])) return set_error(NOVA_ERR_ARG, "%s: out, mass and ws overlap each other", who);
+  }
+  const dim3 grid(chunks, S), block(SC_T);
+  const size_t cstride = shared_centers ? 0 : (size_t)K * 3;
+  if (K <= 8) hipLaunchKernelGGL((soft_cluster_fwd_kernel<8>), grid, block, 0, st, x, c, ws, N, K, cstride, scale);
+  else if (K <= 16) hipLaunchKernelGGL((soft_cluster_fwd_kernel<16>), grid, block, 0, st, x, c, ws, N, K, cstride, scale);
+  else hipLaunchKernelGGL((soft_cluster_fwd_kernel<32>), grid, block, 0, st, x, c, ws, N, K, cstride, scale);
+  hipLaunchKernelGGL(soft_cluster_merge_kernel, dim3((unsigned)(((size_t)S * K + SC_T - 1) / SC_T)), block, 0, st, ws, out, mass, S, K, chunks);
+  return check_launch(who);
+}
+
+int nova_pointset_soft_cluster_bwd(const float* x, const float* c, const float* out, const float* mass, const float* g, const float* gm,
+                                   float* gx, float* gc, float* ws, int S, int N, int K, int shared_centers, float scale, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
   const char* who = "pointset_soft_cluster_bwd";
   if (const int rc = sc_check(who, S, N, K, scale)) return rc;
   if (S <= 0) return 0;
@@ -333,9 +334,9 @@ int pointset_soft_cluster_bwd(const float* x, const float* c, const float* out, 
   const size_t nouts[3] = {nx, no, nw};
   for (int a = 0; a < 3; ++a) {
     for (int b = 0; b < 6; ++b)
-      if (sc_overlap(outs[a], nouts[a], ins[b], nins[b])) return set_error(NOVA_ERR_ARG, "%s: gx, gc or ws overlaps an input", who);
+      if (ranges_overlap(outs[a], nouts[a], ins[b], nins[b])) return set_error(NOVA_ERR_ARG, "%s: gx, gc or ws overlaps an input", who);
     for (int b = a + 1; b < 3; ++b)
-      if (sc_overlap(outs[a], nouts[a], outs[b], nouts[b])) return set_error(NOVA_ERR_ARG, "%s: gx, gc and ws overlap each other", who);
+      if (ranges_overlap(outs[a], nouts[a], outs[b], nouts[b])) return set_error(NOVA_ERR_ARG, "%s: gx, gc and ws overlap each other", who);
   }
   const dim3 grid(chunks, S);
   const size_t cstride = shared_centers ? 0 : (size_t)K * 3;
@@ -348,14 +349,15 @@ int pointset_soft_cluster_bwd(const float* x, const float* c, const float* out, 
   return check_launch(who);
 }
 
-int pointset_soft_cluster_sum_clouds(const float* gc, float* gcs, int S, int K, hipStream_t st) {
+int nova_pointset_soft_cluster_sum_clouds(const float* gc, float* gcs, int S, int K, void* stream) {
+  const hipStream_t st = (hipStream_t)stream;
   const char* who = "pointset_soft_cluster_sum_clouds";
   if (K < 1 || K > SC_MAX_K) return set_error(NOVA_ERR_SHAPE, "%s: K %d outside 1 .. %d (NOVA_SOFT_CLUSTER_MAX_K)", who, K, SC_MAX_K);
   if (S <= 0) return 0;
   if (!gc || !gcs) return set_error(NOVA_ERR_ARG, "%s: null pointer", who);
-  if (sc_overlap(gcs, (size_t)K * 12, gc, (size_t)S * K * 12)) return set_error(NOVA_ERR_ARG, "%s: gcs overlaps gc", who);
+  if (ranges_overlap(gcs, (size_t)K * 12, gc, (size_t)S * K * 12)) return set_error(NOVA_ERR_ARG, "%s: gcs overlaps gc", who);
   hipLaunchKernelGGL(soft_cluster_sum_clouds_kernel, dim3((K * 3 + SC_T - 1) / SC_T), dim3(SC_T), 0, st, gc, gcs, S, K * 3);
   return check_launch(who);
 }
 
-}  // namespace nova
+}  // extern "C"

@@ -28,6 +28,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import hip, metrics
+from ._pointset import _assignment_mode, _at, _check_clamp, _check_clouds, _clouds_per_launch, _launching
 
 # forward launches of nova_pointset_nearest_match and of nova_pointset_matched_dist since import
 stats = {"nearest_match_launches": 0, "matched_dist_launches": 0}
@@ -45,12 +46,9 @@ class _NearestMatch(torch.autograd.Function):
         d = torch.empty(B, N, dtype=torch.float32, device=x.device)
         idx = torch.empty(B, N, dtype=torch.int32, device=x.device)
         if B * N > 0:
-            with torch.cuda.device(x.device):
-                stream = hip.stream_ptr()
-                for s0, s1 in metrics._launches(B, per):
-                    hip.call("nova_pointset_nearest_match", x[s0].data_ptr(), y[s0].data_ptr(), d[s0].data_ptr(), idx[s0].data_ptr(),
-                             s1 - s0, N, M, lo, hi, unit, stream)
-                    stats["nearest_match_launches"] += 1
+            for stream, s0, count in _launching(x.device, B, per):
+                hip.call("nova_pointset_nearest_match", _at(x, s0), _at(y, s0), _at(d, s0), _at(idx, s0), count, N, M, lo, hi, unit, stream)
+                stats["nearest_match_launches"] += 1
         ctx.save_for_backward(x, y, idx)
         ctx.args = (lo, hi, unit, per)
         ctx.mark_non_differentiable(idx)
@@ -66,33 +64,26 @@ class _NearestMatch(torch.autograd.Function):
         gx = torch.empty_like(x)
         gy = torch.empty_like(y) if B * N > 0 else torch.zeros_like(y)
         if B * N > 0:
-            with torch.cuda.device(x.device):
-                stream = hip.stream_ptr()
-                for s0, s1 in metrics._launches(B, per):
-                    hip.call("nova_pointset_nearest_match_bwd", x[s0].data_ptr(), y[s0].data_ptr(), idx[s0].data_ptr(), g[s0].data_ptr(),
-                             gx[s0].data_ptr(), gy[s0].data_ptr(), s1 - s0, N, M, lo, hi, unit, stream)
+            for stream, s0, count in _launching(x.device, B, per):
+                hip.call("nova_pointset_nearest_match_bwd", _at(x, s0), _at(y, s0), _at(idx, s0), _at(g, s0), _at(gx, s0), _at(gy, s0),
+                         count, N, M, lo, hi, unit, stream)
         return gx, gy, None, None, None, None
 
 
 def _nearest_match_arguments(x, y, clamp, unit_norm, return_indices, max_clouds_per_launch):
-    """metrics._check_clouds and the operation's own arguments; everything here holds for CPU tensors too. Returns
+    """_check_clouds and the operation's own arguments; everything here holds for CPU tensors too. Returns
     (lo, hi, clouds per launch)."""
-    metrics._check_clouds(((x, "x"), (y, "y")), letters="B, N", same_clouds=True)
+    _check_clouds(((x, "x"), (y, "y")), letters="B, N", same_clouds=True)
     for t, name in ((x, "x"), (y, "y")):
         if not t.is_floating_point():
             raise ValueError(f"{name}: expected floating-point points, got {t.dtype}")
     if y.shape[1] < 1:
         raise ValueError(f"y: every cloud needs at least one point to match to, got {tuple(y.shape)}")
-    if clamp is not None and not (isinstance(clamp, (int, float)) and not isinstance(clamp, bool) and 0 < clamp < math.inf):
-        raise ValueError(f"clamp must be None or a positive finite number, got {clamp!r}")
+    lo, hi = _check_clamp(clamp)
     for flag, name in ((unit_norm, "unit_norm"), (return_indices, "return_indices")):
         if not isinstance(flag, bool):
             raise ValueError(f"{name} must be a bool, got {flag!r}")
-    if max_clouds_per_launch is None:
-        per = max(1, min(_MAX_CLOUDS_PER_LAUNCH, _PAIRS_PER_LAUNCH // max(1, x.shape[1] * y.shape[1])))
-    else:
-        per = min(metrics._at_least_one(max_clouds_per_launch, "max_clouds_per_launch"), _MAX_CLOUDS_PER_LAUNCH)
-    lo, hi = (-float(clamp), float(clamp)) if clamp is not None else (-math.inf, math.inf)
+    per = _clouds_per_launch(max_clouds_per_launch, _PAIRS_PER_LAUNCH // max(1, x.shape[1] * y.shape[1]), _MAX_CLOUDS_PER_LAUNCH)
     return lo, hi, per
 
 
@@ -131,12 +122,9 @@ class _MatchedDistance(torch.autograd.Function):
         B, n = x.shape[0], x.shape[1]
         d = torch.empty(B, n, dtype=torch.float32, device=x.device)
         if B * n > 0:
-            with torch.cuda.device(x.device):
-                stream = hip.stream_ptr()
-                for s0, s1 in metrics._launches(B, per):
-                    hip.call("nova_pointset_matched_dist", x[s0].data_ptr(), y[s0].data_ptr(), idx[s0].data_ptr(), d[s0].data_ptr(),
-                             s1 - s0, n, lo, hi, floor, stream)
-                    stats["matched_dist_launches"] += 1
+            for stream, s0, count in _launching(x.device, B, per):
+                hip.call("nova_pointset_matched_dist", _at(x, s0), _at(y, s0), _at(idx, s0), _at(d, s0), count, n, lo, hi, floor, stream)
+                stats["matched_dist_launches"] += 1
         ctx.save_for_backward(x, y, idx, inv)
         ctx.args = (lo, hi, floor, per)
         return d
@@ -150,30 +138,22 @@ class _MatchedDistance(torch.autograd.Function):
         g = g.float().contiguous()
         gx, gy = torch.empty_like(x), torch.empty_like(y)
         if B * n > 0:
-            with torch.cuda.device(x.device):
-                stream = hip.stream_ptr()
-                for s0, s1 in metrics._launches(B, per):
-                    hip.call("nova_pointset_matched_dist_bwd", x[s0].data_ptr(), y[s0].data_ptr(), idx[s0].data_ptr(), inv[s0].data_ptr(),
-                             g[s0].data_ptr(), gx[s0].data_ptr(), gy[s0].data_ptr(), s1 - s0, n, lo, hi, floor, stream)
+            for stream, s0, count in _launching(x.device, B, per):
+                hip.call("nova_pointset_matched_dist_bwd", _at(x, s0), _at(y, s0), _at(idx, s0), _at(inv, s0), _at(g, s0), _at(gx, s0),
+                         _at(gy, s0), count, n, lo, hi, floor, stream)
         return gx, gy, None, None, None, None, None, None
 
 
-def _check_clamp(clamp):
-    if clamp is not None and not (isinstance(clamp, (int, float)) and not isinstance(clamp, bool) and 0 < clamp < math.inf):
-        raise ValueError(f"clamp must be None or a positive finite number, got {clamp!r}")
-    return (-float(clamp), float(clamp)) if clamp is not None else (-math.inf, math.inf)
-
-
 def _check_pairs(x, y, names, what):
-    """metrics._check_clouds for two cloud sets that are matched point to point, and the floating dtype."""
-    metrics._check_clouds(((x, names[0]), (y, names[1])), letters="B, n", same_clouds=True, same_points=what)
+    """_check_clouds for two cloud sets that are matched point to point, and the floating dtype."""
+    _check_clouds(((x, names[0]), (y, names[1])), letters="B, n", same_clouds=True, same_points=what)
     for t, name in ((x, names[0]), (y, names[1])):
         if not t.is_floating_point():
             raise ValueError(f"{name}: expected floating-point points, got {t.dtype}")
 
 
 def _matched_distance_arguments(x, y, index, clamp, floor, max_clouds_per_launch):
-    """metrics._check_clouds and the operation's own arguments, the permutation check included; everything here holds for
+    """_check_clouds and the operation's own arguments, the permutation check included; everything here holds for
     CPU tensors too. Returns (lo, hi, floor, clouds per launch)."""
     _check_pairs(x, y, ("x", "y"), "the matched distance")
     B, n = x.shape[0], x.shape[1]
@@ -185,10 +165,7 @@ def _matched_distance_arguments(x, y, index, clamp, floor, max_clouds_per_launch
     lo, hi = _check_clamp(clamp)
     if not (isinstance(floor, (int, float)) and not isinstance(floor, bool) and 0 <= floor < math.inf):
         raise ValueError(f"floor must be a finite number >= 0, got {floor!r}")
-    if max_clouds_per_launch is None:
-        per = max(1, min(_MAX_CLOUDS_PER_LAUNCH, _MATCHED_POINTS_PER_LAUNCH // max(1, n)))
-    else:
-        per = min(metrics._at_least_one(max_clouds_per_launch, "max_clouds_per_launch"), _MAX_CLOUDS_PER_LAUNCH)
+    per = _clouds_per_launch(max_clouds_per_launch, _MATCHED_POINTS_PER_LAUNCH // max(1, n), _MAX_CLOUDS_PER_LAUNCH)
     if B * n > 0:  # a permutation sorts to 0 .. n-1; this also covers the range
         bad = (index.sort(dim=1).values != torch.arange(n, device=index.device)).any(dim=1)
         if bool(bad.any()):
@@ -248,7 +225,7 @@ def emd_loss(pred, target, clamp=2.0, assignment="device", max_rounds=None, roun
     if pred.shape[1] < 1:
         raise ValueError(f"pred: every cloud needs at least one point, got {tuple(pred.shape)}")
     _check_clamp(clamp)
-    device = metrics._assignment_mode(assignment)
+    device = _assignment_mode(assignment)
     if not isinstance(return_assignment, bool):
         raise ValueError(f"return_assignment must be a bool, got {return_assignment!r}")
     p, t = pred.detach(), target.detach()
@@ -298,7 +275,7 @@ def autoregressive_consistency_loss(generated_subsets, target_subsets):
     if not generated_subsets or not target_subsets:
         return torch.tensor(0.0, device=generated_subsets[0].device if generated_subsets else torch.device("cpu"))
     subsets = list(generated_subsets)
-    metrics._check_clouds([(s, f"generated_subsets[{k}]") for k, s in enumerate(subsets)], letters="B, n", same_clouds=True)
+    _check_clouds([(s, f"generated_subsets[{k}]") for k, s in enumerate(subsets)], letters="B, n", same_clouds=True)
     groups = {}
     for i in range(len(subsets) - 1):
         for j in range(i + 1, len(subsets)):
@@ -334,7 +311,7 @@ reference's behaviour: the optimiser never sees emd_weight. There is no wandb lo
     def __init__(self, scheduler, cd_weight=0.1, emd_weight=0.05, diffusion_weight=1.0, autoregressive_weight=0.2,
                  edge_alignment_weight=0.1, emd_assignment="host", emd_gradient=False):
         super().__init__()
-        metrics._assignment_mode(emd_assignment)
+        _assignment_mode(emd_assignment)
         if not isinstance(emd_gradient, bool):
             raise ValueError(f"emd_gradient must be a bool, got {emd_gradient!r}")
         self.scheduler = scheduler

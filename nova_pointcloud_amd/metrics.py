@@ -46,71 +46,9 @@ import numpy as np
 import torch
 
 from . import hip
-
-
-def _points(t, name):
-    if not (torch.is_tensor(t) and t.is_cuda):
-        raise hip.NovaHipError(f"{name}: point-set metrics run on the GPU (got {'a CPU tensor' if torch.is_tensor(t) else type(t).__name__})")
-    if t.dim() != 3 or t.shape[-1] != 3:
-        raise ValueError(f"{name}: expected [B, n, 3] points, got {tuple(t.shape)}")
-    if t.requires_grad and torch.is_grad_enabled():
-        # evaluation metrics: the HIP distance kernels have no backward, so a loss built on them would silently carry no gradient
-        raise hip.NovaHipError(f"{name}: nova_pointcloud_amd.metrics is evaluation-only (no autograd through the HIP kernels); "
-                               "detach the points, or build a training loss on nova_pointcloud_amd.losses")
-    return t.detach().float().contiguous()
-
-
-def _check_clouds(named, letters="S, n", count_range=None, same_clouds=False, same_points=None, same_device=True, finite=True):
-    """ValueError for everything about the point tensors `named`, a sequence of (tensor, name), that does not need the GPU,
-    in one order, each step over all tensors before the next:
-      1. type        every entry is a tensor
-      2. shape       [<letters>, 3]
-      3. counts      same_clouds: equal cloud counts; same_points (what needs them, for the message): equal point counts;
-                     count_range = (kernel name, maximum): 1 .. maximum points per cloud
-      4. device      same_device: all on one device
-      5. finiteness  finite: no NaN and no infinity
-    _points refuses CPU tensors only after this, so all of it holds for CPU tensors too."""
-    for t, name in named:
-        if not torch.is_tensor(t):
-            raise ValueError(f"{name}: expected a tensor [{letters}, 3], got {type(t).__name__}")
-    for t, name in named:
-        if t.dim() != 3 or t.shape[-1] != 3:
-            raise ValueError(f"{name}: expected [{letters}, 3] clouds, got {tuple(t.shape)}")
-    names = " and ".join(name for _, name in named)
-    if same_clouds and len({t.shape[0] for t, _ in named}) > 1:
-        raise ValueError(f"{names} must hold the same number of clouds, got {' and '.join(str(t.shape[0]) for t, _ in named)}")
-    if same_points and len({t.shape[1] for t, _ in named}) > 1:
-        raise ValueError(f"{same_points} needs equal point counts (got {' and '.join(f'{t.shape[1]} ({name})' for t, name in named)})")
-    if count_range is not None:
-        kernel, most = count_range
-        for t, name in named:
-            if not 1 <= t.shape[1] <= most:
-                raise ValueError(f"{name}: the {kernel} kernel takes 1 .. {most} points per cloud, got {t.shape[1]}")
-    if same_device and len({t.device for t, _ in named}) > 1:
-        raise ValueError(f"{names} must be on the same device, got {' and '.join(str(t.device) for t, _ in named)}")
-    if finite:
-        for t, name in named:
-            if not bool(torch.isfinite(t).all()):
-                raise ValueError(f"{name}: points must be finite")
-
-
-def _clouds(named, **checks):
-    """_check_clouds, then _points for each (tensor, name)."""
-    _check_clouds(named, **checks)
-    return [_points(t, name) for t, name in named]
-
-
-def _launches(n_clouds, per, name="max_clouds_per_launch"):
-    """(s0, s1) of the launches that send `n_clouds` clouds out at most `per` at a time. ValueError, at the call and not at
-    the first step, unless per is an integer >= 1."""
-    _at_least_one(per, name)
-    return ((s0, min(n_clouds, s0 + per)) for s0 in range(0, n_clouds, per))
-
-
-def _at_least_one(v, name):
-    if not isinstance(v, int) or isinstance(v, bool) or v < 1:
-        raise ValueError(f"{name} must be an integer >= 1, got {v!r}")
-    return v
+from ._pointset import (ASSIGNMENT_MODES, INTERP_MAX_CHANNELS, INTERP_MAX_POINTS, _INTERP_PAIRS_PER_LAUNCH,  # noqa: F401  (re-exported)
+                        _adaptive_sampling, _assignment_mode, _at, _at_least_one, _check_clamp, _check_clouds, _clouds,
+                        _feature_aware_interpolation, _interp_arguments, _interp_scale, _launches, _launching, _points)
 
 
 def nn_dist(x, y, clamp, unit_norm=False):
@@ -154,15 +92,6 @@ def _assignment_mean(cost):
 
     rows, cols = linear_sum_assignment(cost)
     return cost[rows, cols].mean()
-
-
-ASSIGNMENT_MODES = ("host", "device")
-
-
-def _assignment_mode(assignment):
-    if assignment not in ASSIGNMENT_MODES:
-        raise ValueError(f"assignment must be one of {ASSIGNMENT_MODES}, got {assignment!r}")
-    return assignment == "device"
 
 
 def compute_emd_distance(pred, target, assignment="host"):
@@ -242,8 +171,7 @@ def _assignment_arguments(x, y, clamp, max_rounds, rounds_per_launch):
     _check_clouds(((x, "x"), (y, "y")), letters="B, n", count_range=("assignment", ASSIGN_MAX_POINTS), same_clouds=True,
                   same_points="the assignment")
     n = x.shape[1]
-    if clamp is not None and not (isinstance(clamp, (int, float)) and not isinstance(clamp, bool) and 0 < clamp < math.inf):
-        raise ValueError(f"clamp must be None or a positive finite number, got {clamp!r}")
+    _check_clamp(clamp)
     max_rounds = 64 * n + 1024 if max_rounds is None else _at_least_one(max_rounds, "max_rounds")
     rounds_per_launch = (max(16, _ASSIGN_COLUMN_VISITS_PER_LAUNCH // n) if rounds_per_launch is None
                          else _at_least_one(rounds_per_launch, "rounds_per_launch"))
@@ -527,12 +455,9 @@ def occupancy_grid(pclouds, resolution=28, in_sphere=True, return_nodes=False, m
         if N == 0:
             raise ValueError("occupancy_grid: empty clouds (0 points)")
         per = max_clouds_per_launch if max_clouds_per_launch is not None else max(1, _OCC_POINTS_PER_LAUNCH // N)
-        with torch.cuda.device(x.device):
-            st = hip.stream_ptr()
-            for s0, s1 in _launches(S, per):
-                hip.call("nova_pointset_occupancy_grid", x[s0].data_ptr(), counters.data_ptr(), bernoulli.data_ptr(),
-                         nodes[s0].data_ptr() if return_nodes else None, outside.data_ptr(), s1 - s0, N, R, 1 if in_sphere else 0,
-                         int(workgroups), st)
+        for stream, s0, count in _launching(x.device, S, per):
+            hip.call("nova_pointset_occupancy_grid", _at(x, s0), counters.data_ptr(), bernoulli.data_ptr(), _at(nodes, s0), outside.data_ptr(),
+                     count, N, R, 1 if in_sphere else 0, int(workgroups), stream)
     out = {"counters": counters, "bernoulli": bernoulli, "outside": int(outside)}
     if return_nodes:
         out["nodes"] = nodes
@@ -641,15 +566,13 @@ def farthest_point_sample(points, n_samples, start=0, return_distances=False, ma
     x = _points(points, "points")
     S, N, n = x.shape[0], x.shape[1], n_samples
     per = max_clouds_per_launch if max_clouds_per_launch is not None else max(1, _FPS_POINT_STEPS_PER_LAUNCH // (N * n))
-    launches = _launches(S, per)
+    launches = _launching(x.device, S, per)
     idx = torch.empty(S, n, dtype=torch.int32, device=x.device)
     dist = torch.empty(S, n, dtype=torch.float32, device=x.device) if return_distances else None
     st = st.to(device=x.device, dtype=torch.int32) if st is not None else None
-    with torch.cuda.device(x.device):
-        stream = hip.stream_ptr()
-        for s0, s1 in launches:
-            hip.call("nova_pointset_farthest_point_sample", x[s0].data_ptr(), st[s0:].data_ptr() if st is not None else None,
-                     idx[s0].data_ptr(), dist[s0].data_ptr() if return_distances else None, s1 - s0, N, n, stream)
+    for stream, s0, count in launches:
+        hip.call("nova_pointset_farthest_point_sample", _at(x, s0), st[s0:].data_ptr() if st is not None else None, _at(idx, s0), _at(dist, s0),
+                 count, N, n, stream)
     return (idx.long(), dist) if return_distances else idx.long()
 
 
@@ -742,14 +665,11 @@ def knn_points(x, y=None, k=8, exclude_self=None, return_distances=True, max_clo
     ys = xs if y is None else _points(y, "y")
     S, N, M = xs.shape[0], xs.shape[1], ys.shape[1]
     per = max_clouds_per_launch if max_clouds_per_launch is not None else max(1, _KNN_CANDIDATES_PER_LAUNCH // (N * M))
-    launches = _launches(S, per)
+    launches = _launching(xs.device, S, per)
     idx = torch.empty(S, N, k, dtype=torch.int32, device=xs.device)
     d2 = torch.empty(S, N, k, dtype=torch.float32, device=xs.device) if return_distances else None
-    with torch.cuda.device(xs.device):
-        stream = hip.stream_ptr()
-        for s0, s1 in launches:
-            hip.call("nova_pointset_knn", xs[s0].data_ptr(), ys[s0].data_ptr(), idx[s0].data_ptr(),
-                     d2[s0].data_ptr() if return_distances else None, s1 - s0, N, M, k, 1 if exclude_self else 0, stream)
+    for stream, s0, count in launches:
+        hip.call("nova_pointset_knn", _at(xs, s0), _at(ys, s0), _at(idx, s0), _at(d2, s0), count, N, M, k, 1 if exclude_self else 0, stream)
     return (idx.long(), d2) if return_distances else idx.long()
 
 
@@ -765,52 +685,6 @@ def local_density(points, k_neighbors=8):
 # ----------------------------------------------------------------------------------------------------
 # distance-weighted interpolation and adaptive sampling
 # ----------------------------------------------------------------------------------------------------
-INTERP_MAX_POINTS = 65536  # == NOVA_INTERP_MAX_POINTS of include/nova_hip.h
-INTERP_MAX_CHANNELS = 8  # == NOVA_INTERP_MAX_CHANNELS of include/nova_hip.h
-# (query, source) pairs (clouds x queries x sources) per launch, ~8.6e9. Re-derived from the measured launches of
-# tools/interp_bench.py (profiles/interp_bench.json): 32 x 1024 queries on 2048 sources, 512 workgroups, run in 0.21 ms
-# (3.1e11 pairs/s) and 7500 queries on 15 000 sources, 118 workgroups on 256 compute units, in 0.58 ms, the longest single
-# launch under this cap (1.9e11 pairs/s). Both are too small to fill the chip, so they are far below the instruction-count
-# estimate (about 46 vector issue slots per pair: ~1.7e12 pairs/s), and a full launch has not been timed; at the better of
-# the two measured rates 2^33 pairs are 28 ms, at the estimate 5 ms. A cloud is at most 2^32 pairs, so a launch holds at
-# least two (distance-weighted interpolation).
-_INTERP_PAIRS_PER_LAUNCH = 1 << 33
-
-
-def _interp_scale(temperature):
-    """log2(e) / temperature as the float32 the kernel takes. ValueError unless temperature is a real number > 0 (inf
-    allowed: the plain mean) and that quotient is finite in float32."""
-    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not temperature > 0:
-        raise ValueError(f"temperature must be a real number > 0 (inf for the plain mean), got {temperature!r}")
-    with np.errstate(over="ignore"):
-        scale = float(np.float32(np.float64(math.log2(math.e)) / np.float64(temperature)))  # one division in float64, one rounding
-    if not math.isfinite(scale):
-        raise ValueError(f"temperature {temperature!r} is too small: log2(e) / temperature is not finite in float32")
-    return scale
-
-
-def _interp_arguments(queries, points, values):
-    """_check_clouds and the checks of `values` that do not need the GPU. Returns the channel count C."""
-    _check_clouds([(queries, "queries"), (points, "points")], letters="S, N", count_range=("interpolation", INTERP_MAX_POINTS),
-                  same_clouds=True)
-    if values is None:
-        return 3
-    if not torch.is_tensor(values):
-        raise ValueError(f"values: expected a tensor [S, N, C], got {type(values).__name__}")
-    S, N = points.shape[0], points.shape[1]
-    if values.dim() != 3 or tuple(values.shape[:2]) != (S, N):
-        raise ValueError(f"values: expected [{S}, {N}, C] (one row per source point), got {tuple(values.shape)}")
-    if not 1 <= values.shape[2] <= INTERP_MAX_CHANNELS:
-        raise ValueError(f"values: the interpolation kernel takes 1 .. {INTERP_MAX_CHANNELS} channels, got {values.shape[2]}")
-    if not values.dtype.is_floating_point:
-        raise ValueError(f"values: expected a floating-point tensor, got {values.dtype}")
-    if values.device != points.device:
-        raise ValueError(f"values and points must be on the same device, got {values.device} and {points.device}")
-    if not bool(torch.isfinite(values).all()):
-        raise ValueError("values: values must be finite")
-    return values.shape[2]
-
-
 def kernel_interpolate(queries, points, values=None, temperature=1.0, max_clouds_per_launch=None):
     """Distance-weighted interpolation on the GPU: float32 [S, T, C] on the input's device, row (s, i) the average of
     values[s] [N, C] over ALL source points points[s] [N, 3], weighted by softmax_j(-|queries[s, i] - points[s, j]| /
@@ -839,27 +713,11 @@ def kernel_interpolate(queries, points, values=None, temperature=1.0, max_clouds
         vs = values.detach().float().contiguous()
     S, T, N = qs.shape[0], qs.shape[1], ps.shape[1]
     per = max_clouds_per_launch if max_clouds_per_launch is not None else max(1, _INTERP_PAIRS_PER_LAUNCH // (T * N))
-    launches = _launches(S, per)
+    launches = _launching(qs.device, S, per)
     out = torch.empty(S, T, C, dtype=torch.float32, device=qs.device)
-    with torch.cuda.device(qs.device):
-        stream = hip.stream_ptr()
-        for s0, s1 in launches:
-            hip.call("nova_pointset_kernel_interpolate", qs[s0].data_ptr(), ps[s0].data_ptr(), vs[s0].data_ptr() if vs is not None else None,
-                     out[s0].data_ptr(), s1 - s0, T, N, C, scale, stream)
+    for stream, s0, count in launches:
+        hip.call("nova_pointset_kernel_interpolate", _at(qs, s0), _at(ps, s0), _at(vs, s0), _at(out, s0), count, T, N, C, scale, stream)
     return out
-
-
-def _cyclic(points, target_size):
-    """points [S, N, 3] repeated along the point axis and cut to target_size (pure torch)."""
-    return points.repeat(1, target_size // points.shape[1] + 1, 1)[:, :target_size]
-
-
-def _sampling_arguments(points, name, target_size, temperature):
-    _check_clouds([(points, name)], letters="S, N", finite=False)
-    _at_least_one(target_size, "target_size")
-    if points.shape[1] < 1:
-        raise ValueError(f"{name}: empty clouds (0 points)")
-    _interp_scale(temperature)
 
 
 def feature_aware_interpolation(points, target_size, temperature=1.0, generator=None):
@@ -869,12 +727,7 @@ def feature_aware_interpolation(points, target_size, temperature=1.0, generator=
     torch.randperm(N, generator=generator) shared by all clouds (a CPU generator, or None for the global one), as in the
     reference, and each becomes kernel_interpolate's softmax(-distance / temperature) average of ALL N points (GPU only;
     float32). The reference's temperature is 1; its topk(8) is dead code and is not reproduced."""
-    _sampling_arguments(points, "points", target_size, temperature)
-    N = points.shape[1]
-    if N <= target_size:
-        return _cyclic(points, target_size)
-    perm = torch.randperm(N, generator=generator)[:target_size].to(points.device)
-    return kernel_interpolate(points[:, perm], points, temperature=temperature)
+    return _feature_aware_interpolation(kernel_interpolate, points, target_size, temperature, generator)
 
 
 def adaptive_sampling(subset, target_size, temperature=1.0, generator=None):
@@ -885,14 +738,7 @@ def adaptive_sampling(subset, target_size, temperature=1.0, generator=None):
     of the result stays well spread (GPU only).
     DEVIATION, on purpose: the reference sends the sparse case to its farthest_point_sampling with more samples than
     points, which that body cannot deliver (include/nova_hip.h, nova_pointset_kernel_interpolate)."""
-    _sampling_arguments(subset, "subset", target_size, temperature)
-    S, N = subset.shape[0], subset.shape[1]
-    if N == target_size:
-        return subset
-    if N > target_size:
-        return feature_aware_interpolation(subset, target_size, temperature=temperature, generator=generator)
-    order = farthest_point_sample(subset, N)[:, torch.arange(target_size, device=subset.device) % N]
-    return torch.gather(subset, 1, order[:, :, None].expand(S, target_size, 3))
+    return _adaptive_sampling(kernel_interpolate, farthest_point_sample, subset, target_size, temperature, generator)
 
 
 NORMALIZE_MODES = ("none", "unit_sphere", "unit_cube")

@@ -15,6 +15,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import hip, metrics
+from ._pointset import _at, _at_least_one, _check_clouds, _clouds_per_launch, _launching
 
 NEIGHBOR_MAX_CHANNELS = 4096  # == NOVA_NEIGHBOR_MAX_CHANNELS of include/nova_hip.h
 _MAX_CLOUDS_PER_CALL = 65535  # clouds go in grid.y
@@ -76,12 +77,9 @@ class _Aggregate(torch.autograd.Function):
         S, M, C = f.shape
         N, k = idx.shape[1], idx.shape[2]
         out = torch.empty(S, N, C, dtype=torch.float32, device=f.device)
-        with torch.cuda.device(f.device):
-            stream = hip.stream_ptr()
-            for s0, s1 in metrics._launches(S, per):
-                hip.call("nova_pointset_neighbor_aggregate", f[s0].data_ptr(), idx[s0].data_ptr(), w[s0].data_ptr() if w is not None else None,
-                         out[s0].data_ptr(), s1 - s0, N, M, k, C, stream)
-                stats["forward_launches"] += 1
+        for stream, s0, count in _launching(f.device, S, per):
+            hip.call("nova_pointset_neighbor_aggregate", _at(f, s0), _at(idx, s0), _at(w, s0), _at(out, s0), count, N, M, k, C, stream)
+            stats["forward_launches"] += 1
         ctx.save_for_backward(f, idx, w)  # [S, M, C], [S, N, k], [S, N, k]: nothing of size N k C
         ctx.per = per
         return out
@@ -102,18 +100,14 @@ class _Aggregate(torch.autograd.Function):
             # the inverse neighbour list exists only while the feature gradient is formed
             offsets = torch.empty(S, M + 1, dtype=torch.int32, device=f.device) if want_f else None
             edges = torch.empty(S, N * k, dtype=torch.int32, device=f.device) if want_f else None
-            at = lambda t, s0: t[s0].data_ptr() if t is not None else None
-            with torch.cuda.device(f.device):
-                stream = hip.stream_ptr()
-                for s0, s1 in metrics._launches(S, per):
-                    if want_f:
-                        hip.call("nova_pointset_neighbor_inverse", idx[s0].data_ptr(), offsets[s0].data_ptr(), edges[s0].data_ptr(),
-                                 s1 - s0, N, M, k, stream)
-                        stats["inverse_launches"] += 1
-                    hip.call("nova_pointset_neighbor_aggregate_bwd", f[s0].data_ptr(), idx[s0].data_ptr(), at(w, s0), g[s0].data_ptr(),
-                             at(offsets, s0), at(edges, s0), at(gf, s0), at(gw, s0), s1 - s0, N, M, k, C, stream)
-                    stats["feature_grad_launches"] += 1 if want_f else 0
-                    stats["weight_grad_launches"] += 1 if want_w else 0
+            for stream, s0, count in _launching(f.device, S, per):
+                if want_f:
+                    hip.call("nova_pointset_neighbor_inverse", _at(idx, s0), _at(offsets, s0), _at(edges, s0), count, N, M, k, stream)
+                    stats["inverse_launches"] += 1
+                hip.call("nova_pointset_neighbor_aggregate_bwd", _at(f, s0), _at(idx, s0), _at(w, s0), _at(g, s0), _at(offsets, s0),
+                         _at(edges, s0), _at(gf, s0), _at(gw, s0), count, N, M, k, C, stream)
+                stats["feature_grad_launches"] += 1 if want_f else 0
+                stats["weight_grad_launches"] += 1 if want_w else 0
         return gf, None, gw, None
 
 
@@ -133,16 +127,14 @@ def neighbor_aggregate(features, idx, weights=None, max_clouds_per_launch=None):
     `max_clouds_per_launch`, every position in the batch and every run. A kernel whose outputs no input needs is not
     launched (`stats`). Default launch split: _NEIGHBOR_BYTES_PER_LAUNCH and _NEIGHBOR_COMPARES_PER_LAUNCH above."""
     _aggregate_arguments(features, idx, weights)
-    if max_clouds_per_launch is not None:
-        metrics._at_least_one(max_clouds_per_launch, "max_clouds_per_launch")
+    (M, C), (N, k) = features.shape[1:], idx.shape[1:]
+    per = _clouds_per_launch(max_clouds_per_launch, _default_clouds_per_launch(N, M, k, C), _MAX_CLOUDS_PER_CALL)
     for t, name in [(features, "features"), (idx, "idx")] + ([(weights, "weights")] if weights is not None else []):
         if not t.is_cuda:
             raise hip.NovaHipError(f"{name}: the neighbourhood aggregation runs on the GPU (got a CPU tensor)")
     fs = features.float().contiguous()
     ix = idx.to(torch.int32).contiguous()
     ws = weights.float().contiguous() if weights is not None else None
-    (M, C), (N, k) = fs.shape[1:], ix.shape[1:]
-    per = _default_clouds_per_launch(N, M, k, C) if max_clouds_per_launch is None else min(max_clouds_per_launch, _MAX_CLOUDS_PER_CALL)
     return _Aggregate.apply(fs, ix, ws, per)
 
 
@@ -166,11 +158,11 @@ def edge_features(points, features, k=8, max_clouds_per_launch=None):
     ties go to the lowest index (metrics.knn_points). Differentiable in features, not in points: the reference's topk
     indices carry no gradient either. DEVIATION: the reference's gather does not run as written for [B, N, C] features;
     this is its comment (centre feature minus the mean of the k nearest neighbours' features)."""
-    metrics._check_clouds([(points, "points")], letters="S, N", count_range=("kNN", metrics.KNN_MAX_POINTS))
+    _check_clouds([(points, "points")], letters="S, N", count_range=("kNN", metrics.KNN_MAX_POINTS))
     _feature_rows(points, features, "features", "points")
-    metrics._at_least_one(k, "k")
+    _at_least_one(k, "k")
     if max_clouds_per_launch is not None:
-        metrics._at_least_one(max_clouds_per_launch, "max_clouds_per_launch")
+        _at_least_one(max_clouds_per_launch, "max_clouds_per_launch")
     pts = points.detach()
     idx = metrics.knn_points(pts, pts, k=min(k, points.shape[1]), exclude_self=False, return_distances=False,
                              max_clouds_per_launch=max_clouds_per_launch)
@@ -185,8 +177,7 @@ def knn_interpolate(queries, points, values, k=3, eps=1e-8):
     differentiable in queries and points through the weight gradient of neighbor_aggregate, and in values through its
     feature gradient. A query coincident with a source has d2 = 0 there and weight 1 / eps before normalisation: finite
     values and gradients for eps > 0."""
-    metrics._check_clouds([(queries, "queries"), (points, "points")], letters="S, N", count_range=("kNN", metrics.KNN_MAX_POINTS),
-                          same_clouds=True)
+    _check_clouds([(queries, "queries"), (points, "points")], letters="S, N", count_range=("kNN", metrics.KNN_MAX_POINTS), same_clouds=True)
     _feature_rows(points, values, "values", "points")
     N = points.shape[1]
     if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= min(metrics.KNN_MAX_K, N):

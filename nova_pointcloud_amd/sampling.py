@@ -15,6 +15,8 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import hip, metrics
+from ._pointset import (_INTERP_PAIRS_PER_LAUNCH, _adaptive_sampling, _at, _clouds_per_launch, _feature_aware_interpolation,
+                        _interp_arguments, _interp_scale, _launching)
 
 # launches since import: forward launches of nova_pointset_kernel_interpolate_stats, and launches of the two backward
 # kernels (query side: gq; source side: gp and gv), which are skipped when no input needs their outputs
@@ -29,12 +31,10 @@ class _Interpolate(torch.autograd.Function):
         out = torch.empty(S, T, C, dtype=torch.float32, device=q.device)
         m = torch.empty(S, T, dtype=torch.float32, device=q.device)
         l = torch.empty(S, T, dtype=torch.float32, device=q.device)
-        with torch.cuda.device(q.device):
-            stream = hip.stream_ptr()
-            for s0, s1 in metrics._launches(S, per):
-                hip.call("nova_pointset_kernel_interpolate_stats", q[s0].data_ptr(), p[s0].data_ptr(), v[s0].data_ptr() if v is not None else None,
-                         out[s0].data_ptr(), m[s0].data_ptr(), l[s0].data_ptr(), s1 - s0, T, N, C, scale, stream)
-                stats["forward_launches"] += 1
+        for stream, s0, count in _launching(q.device, S, per):
+            hip.call("nova_pointset_kernel_interpolate_stats", _at(q, s0), _at(p, s0), _at(v, s0), _at(out, s0), _at(m, s0), _at(l, s0),
+                     count, T, N, C, scale, stream)
+            stats["forward_launches"] += 1
         ctx.save_for_backward(q, p, v, out, m, l)  # [S, T | N, 3 | C] and [S, T]: nothing of size T N
         ctx.args = (scale, per)
         return out
@@ -53,15 +53,11 @@ class _Interpolate(torch.autograd.Function):
         gp = torch.empty_like(p) if want_p else None
         gv = torch.empty_like(v) if v is not None and (want_p or want_v) else None  # the source-side kernel forms gp and gv together
         if want_q or want_p or want_v:
-            at = lambda t, s0: t[s0].data_ptr() if t is not None else None
-            with torch.cuda.device(q.device):
-                stream = hip.stream_ptr()
-                for s0, s1 in metrics._launches(S, per):
-                    hip.call("nova_pointset_kernel_interpolate_bwd", q[s0].data_ptr(), p[s0].data_ptr(), at(v, s0), out[s0].data_ptr(),
-                             m[s0].data_ptr(), l[s0].data_ptr(), g[s0].data_ptr(), at(gq, s0), at(gp, s0), at(gv, s0), s1 - s0, T, N, C,
-                             scale, stream)
-                    stats["query_side_launches"] += 1 if want_q else 0
-                    stats["source_side_launches"] += 1 if want_p or want_v else 0
+            for stream, s0, count in _launching(q.device, S, per):
+                hip.call("nova_pointset_kernel_interpolate_bwd", _at(q, s0), _at(p, s0), _at(v, s0), _at(out, s0), _at(m, s0), _at(l, s0),
+                         _at(g, s0), _at(gq, s0), _at(gp, s0), _at(gv, s0), count, T, N, C, scale, stream)
+                stats["query_side_launches"] += 1 if want_q else 0
+                stats["source_side_launches"] += 1 if want_p or want_v else 0
         return gq, gp, gv if want_v else None, None, None
 
 
@@ -79,8 +75,8 @@ def kernel_interpolate(queries, points, values=None, temperature=1.0, max_clouds
     (gq), one per source over all queries in increasing index (gp and gv), without atomics, so all three gradients are
     bitwise the same for every `max_clouds_per_launch`, every position in the batch and every run. A kernel whose outputs
     no input needs is not launched (`stats`). Launch splits follow the forward's."""
-    metrics._interp_arguments(queries, points, values)
-    scale = metrics._interp_scale(temperature)
+    _interp_arguments(queries, points, values)
+    scale = _interp_scale(temperature)
     named = [(queries, "queries"), (points, "points")] + ([(values, "values")] if values is not None else [])
     for t, name in named:
         if not t.is_cuda:
@@ -88,11 +84,7 @@ def kernel_interpolate(queries, points, values=None, temperature=1.0, max_clouds
     qs = queries.float().contiguous()
     ps = qs if points is queries else points.float().contiguous()
     vs = values.float().contiguous() if values is not None else None
-    S, T, N = qs.shape[0], qs.shape[1], ps.shape[1]
-    if max_clouds_per_launch is None:
-        per = max(1, metrics._INTERP_PAIRS_PER_LAUNCH // (T * N))
-    else:
-        per = metrics._at_least_one(max_clouds_per_launch, "max_clouds_per_launch")
+    per = _clouds_per_launch(max_clouds_per_launch, _INTERP_PAIRS_PER_LAUNCH // (qs.shape[1] * ps.shape[1]))
     return _Interpolate.apply(qs, ps, vs, scale, per)
 
 
@@ -102,12 +94,7 @@ def feature_aware_interpolation(points, target_size, temperature=1.0, generator=
     torch; works on CPU tensors); otherwise target_size of them, picked by one torch.randperm(N, generator=generator)
     shared by all clouds, become kernel_interpolate's average of ALL N points, and the gradient reaches the points both as
     sources and, through the indexing, as queries."""
-    metrics._sampling_arguments(points, "points", target_size, temperature)
-    N = points.shape[1]
-    if N <= target_size:
-        return metrics._cyclic(points, target_size)
-    perm = torch.randperm(N, generator=generator)[:target_size].to(points.device)
-    return kernel_interpolate(points[:, perm], points, temperature=temperature)
+    return _feature_aware_interpolation(kernel_interpolate, points, target_size, temperature, generator)
 
 
 def adaptive_sampling(subset, target_size, temperature=1.0, generator=None):
@@ -115,11 +102,5 @@ def adaptive_sampling(subset, target_size, temperature=1.0, generator=None):
     with a gradient into the subset: N == target_size returns the input itself, N > target_size
     feature_aware_interpolation, N < target_size the points in farthest-point order repeated cyclically: the order is
     found on the detached points (indices carry no gradient) and the gather is torch's."""
-    metrics._sampling_arguments(subset, "subset", target_size, temperature)
-    S, N = subset.shape[0], subset.shape[1]
-    if N == target_size:
-        return subset
-    if N > target_size:
-        return feature_aware_interpolation(subset, target_size, temperature=temperature, generator=generator)
-    order = metrics.farthest_point_sample(subset.detach(), N)[:, torch.arange(target_size, device=subset.device) % N]
-    return torch.gather(subset, 1, order[:, :, None].expand(S, target_size, 3))
+    detached_order = lambda s, n: metrics.farthest_point_sample(s.detach(), n)  # indices carry no gradient
+    return _adaptive_sampling(kernel_interpolate, detached_order, subset, target_size, temperature, generator)
