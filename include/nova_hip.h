@@ -604,6 +604,78 @@ int nova_pointset_soft_cluster_bwd(const float* x, const float* c, const float* 
                                    float scale, void* stream);
 int nova_pointset_soft_cluster_sum_clouds(const float* gc, float* gcs, int S, int K, void* stream);
 
+/* Depth-aware 3-D positional encoding, forward and backward: every coordinate of every point x [S, N, 3] (float32), times a
+ * learnable scale, encoded into out [S, N, E] (float32) with sines and cosines over F = E / 6 (integer division)
+ * frequencies, optionally added onto base [S, N, E]. It is the last custom operation of the reference's
+ * PointCloudTransformer.forward in front of the soft clustering above: DepthAwarePositionalEncoding,
+ * diffnext/models/transformers/transformer_pointcloud_nova.py:349-389, applied at :456-458 as x = x + depth_pe (a
+ * zeros([B, N, E]), six strided slice assignments pe[:, :, k::6] each with its own [B, N, E / 6] division and sine or cosine,
+ * a separate add; autograd keeps the six arguments). Neither pass stores anything of size N E here.
+ * scale [3]: a DEVICE pointer to the three learnable scales (scale_x, scale_y, scale_z, :363-365), so the caller never
+ * synchronises. div [F]: a device table of divisors, the caller's; the reference's is
+ * (10000.0 ** (torch.arange(0, E, 2) / E))[:F] in float32 (:358-360), which encoding.py builds by those very torch ops. The
+ * kernels are general over its values. base may be NULL.
+ * nova_pointset_posenc: for row i of the S N rows, coordinate c in {0, 1, 2} and frequency f < F, every operation rounded
+ *   once to float32 and nothing fused:
+ *     s_c   = x[i, c] * scale[c]
+ *     a_cf  = s_c / div[f]                      IEEE division, no reciprocal approximation
+ *     pe[i, 6 f + 2 c]     = sinf(a_cf)         sinf, cosf: the device math library's accurate sincosf over the whole
+ *     pe[i, 6 f + 2 c + 1] = cosf(a_cf)         float32 range; never the native __sinf / __cosf, no fast-math flag
+ *     pe[i, ch] = +0 for 6 F <= ch < E          the tail channels
+ *     out = pe, or base + pe                    one rounded addition per channel when base is given (tail: base + (+0))
+ *   EXTENSION: the reference raises where tail channels exist (E % 6 != 0: pe[:, :, 0::6] then has one slot more than
+ *   div_term[:E // 6]); here they are defined as +0. The reference also cannot run on a GPU tensor (div_term is a plain CPU
+ *   attribute), and its torch.stack([scale_x, scale_y, scale_z], dim=0) is [3, 1], which broadcasts against [B, N, 3] along
+ *   the point axis (:372: it raises unless N is 1 or 3); the scales here multiply per coordinate, the evident intent. With
+ *   those three repaired the arithmetic above is what its CPU float32 ops compute.
+ *   Non-finite points are not checked (a training path); NaN comes out as in torch.
+ * nova_pointset_posenc_bwd: from g [S, N, E] = dLoss/dout and the forward's x, scale and div: gx [S, N, 3] and the PER-CLOUD
+ *   scale gradient gs [S, 3] (float32). Every s_c, a_cf, sine and cosine is recomputed as above, bit for bit. Then
+ *     u_cf     = fmaf(-g[i, 6 f + 2 c + 1], sinf(a_cf), g[i, 6 f + 2 c] * cosf(a_cf))    the product rounded once
+ *     term_cf  = u_cf / div[f]                   IEEE division
+ *     t_ic     = sum_f term_cf                   order below
+ *     gx[i, c] = scale[c] * t_ic
+ *     gs[s, c] = sum over the rows i of cloud s of x[i, c] * t_ic, each step acc = fmaf(x[i, c], t_ic, acc); order below
+ *   The tail channels of g are not read. The gradient of base is g itself: no kernel runs for it.
+ *   Order of the sums (part of the definition: it fixes the bits; it depends on (N, E) alone, never on S, the launch split
+ *   or the cloud's position):
+ *     over f within a row: the 3 F (sin, cos) pairs of a row are numbered j = 3 f + c. Lane l of one wave of 64 adds to +0,
+ *       per coordinate c, the terms of its pairs j = l, l + 64, l + 128, ... with j % 3 == c in ascending j. The 64 lane
+ *       sums of a coordinate are added by six pairwise steps in which both partners take a + b: lanes i <-> 7 - i inside
+ *       each group of 8, then xor 1, xor 2, i <-> 15 - i inside each row of 16, rows 0|1 and 2|3 of 16 lanes, the two halves
+ *       of 32 (the pairing of nova_pointset_soft_cluster).
+ *     over the rows of a chunk: the cloud is cut into chunks of NOVA_POSENC_CHUNK = 32 consecutive rows. Inside a chunk
+ *       starting at row b, wave w of 4 accumulates from +0 the rows b + w, b + w + 4, ... , b + w + 28 in that order, skipping
+ *       those past N - 1 (a wave with no row keeps +0); the four waves are added as ((w0 + w1) + w2) + w3.
+ *     over the chunks of a cloud: the chunk sums are added to +0 in ascending chunk order, through the workspace.
+ *   No atomics.
+ *   A NULL gx or gs means "not wanted" and the work that only serves it is skipped; they may not both be NULL.
+ *   ws: a caller-provided workspace of S * ceil(N / NOVA_POSENC_CHUNK) * 3 floats, read and written only when gs is given;
+ *   its contents after the call are unspecified.
+ *   The gradient of the scales [3] is the sum of gs over the clouds in ascending cloud order, formed ONCE after every launch
+ *   has written its clouds: nova_pointset_soft_cluster_sum_clouds(gs, out3, S, K = 1, stream) has exactly that contract
+ *   (gcs[0, j] = the sum of gc[s, 0, j] added to +0 in ascending s) and is what encoding.py calls; there is no second kernel.
+ * Consequences: out, gx and gs of a cloud depend on (x[s], scale, div, base[s] or g[s], N, E) alone: bitwise the same for
+ * every batch, launch split, position in the batch and run. out with base is bitwise the float32 sum base + out-without-base.
+ * x == 0 gives exactly +0 in the sine channels and 1 in the cosine channels (a negative scale makes the argument 0 * scale = -0
+ * and its sine -0, as IEEE and torch have it).
+ * Limits: 6 <= E <= NOVA_POSENC_MAX_DIM; 1 <= N <= NOVA_POSENC_MAX_POINTS; clouds in grid.y, at most 65535 per call; element
+ * offsets are 64-bit throughout (S N E passes 2^31).
+ * Errors of both entries, in this order, before any device work: NOVA_ERR_SHAPE for E outside its range, for N outside its
+ * range, for S > 65535. S <= 0 returns 0 after these, before any pointer is looked at. Then NOVA_ERR_ARG for a null x,
+ * scale, div or out (forward), a null x, scale, div or g (backward); backward only: NOVA_ERR_ARG for gx and gs both NULL,
+ * then for gs given with a null ws; last, NOVA_ERR_ARG when an output (out; gx, gs, ws) overlaps an input (x, scale, div,
+ * base; x, scale, div, g) or another output.
+ * Added without a version bump (the number is pinned by the tests of three earlier entries; a library without the new
+ * symbols fails to bind, loudly). */
+#define NOVA_POSENC_MAX_DIM 4096
+#define NOVA_POSENC_MAX_POINTS 65536
+#define NOVA_POSENC_CHUNK 32
+int nova_pointset_posenc(const float* x, const float* scale, const float* div, const float* base, float* out, int S, int N,
+                         int E, void* stream);
+int nova_pointset_posenc_bwd(const float* x, const float* scale, const float* div, const float* g, float* gx, float* gs,
+                             float* ws, int S, int N, int E, void* stream);
+
 /* Nearest match with indices, and its backward: the primitive under the Chamfer-type training losses of the reference,
  * robust_chamfer_distance on distChamfer (train_newloss.py:316-349) and the edge-consistency term (train_newloss.py:449-457:
  * torch.cdist(subset1, subset2).min(dim=1), mean), which in PyTorch keep a [B, N, M] cdist matrix alive for the backward.
