@@ -178,6 +178,9 @@ int nova_row_norm_bwd(const void* x, const void* dy, const float* gamma, const f
 /* ---- LayerNorm family -----------------------------------------------------------------------
  * y = LN(in[gather ? gather[r] : r]; eps) [* gamma + beta] [* (1 + mod[r, scale_off..]) +
  * mod[r, shift_off..]] [* mod[r, gate_off..]] [+ res[r]] -> out[r]. Offsets < 0 disable a term.
+ * in is indexed by source row, res and mod by output row. Every term's D columns lie inside a
+ * modulation row: off + D <= mod_ld, NOVA_ERR_SHAPE otherwise (nova_row_norm_chain and
+ * nova_row_norm_bwd refuse the same).
  * Replaces: Block post-norm residual `norm(attn(x)).add_(x)` vision_transformer.py:78-82,91-92;
  * AdaLayerNormZero.forward normalization.py:34-36; DiffusionBlock `norm2(proj(h)).mul(gate)
  * .add_(x)` diffusion_mlp.py:52-53; final encoder norm vision_transformer.py:146 fused with the

@@ -108,6 +108,9 @@ int row_norm(const RowNormArgs& a, int dtype, hipStream_t st) {
   if (a.mod && (a.mod_ld % vec || (a.scale_off >= 0 && (a.scale_off % vec || a.shift_off % vec || a.shift_off < 0)) ||
                 (a.gate_off >= 0 && a.gate_off % vec)))
     return set_error(NOVA_ERR_SHAPE, "row_norm: modulation offsets must be multiples of %d", vec);
+  if (a.mod)  // every term's D columns inside a modulation row (as row_norm_bwd)
+    for (int off : {a.scale_off, a.shift_off, a.gate_off})
+      if (off >= 0 && (long)off + a.D > a.mod_ld) return set_error(NOVA_ERR_SHAPE, "row_norm: modulation offset %d + D %d exceeds the row stride %ld", off, a.D, (long)a.mod_ld);
   if ((a.gamma == nullptr) != (a.beta == nullptr)) return set_error(NOVA_ERR_ARG, "row_norm: gamma/beta must come together");
   if (a.out8 && (dtype != NOVA_BF16 || !a.out8_scale)) return set_error(NOVA_ERR_ARG, "row_norm: the fp8 side output needs bf16 rows and a scale buffer");
   dim3 grid((unsigned)((a.rows + 3) / 4));
@@ -163,6 +166,11 @@ int row_norm_chain(const RowNormArgs& a2, const RowNormArgs& a1, void* x_new_out
     return set_error(NOVA_ERR_ARG, "row_norm_chain: first norm = gate + residual, second = scale / shift modulate");
   if (a2.mod_ld % 8 || a2.gate_off % 8 || a1.mod_ld % 8 || a1.scale_off % 8 || a1.shift_off % 8)
     return set_error(NOVA_ERR_SHAPE, "row_norm_chain: modulation offsets must be multiples of 8");
+  for (int i = 0; i < 3; ++i) {  // every term's D columns inside its modulation row (as row_norm_bwd)
+    const int off = i == 0 ? a2.gate_off : (i == 1 ? a1.scale_off : a1.shift_off);
+    const long ld = i == 0 ? a2.mod_ld : a1.mod_ld;
+    if ((long)off + a2.D > ld) return set_error(NOVA_ERR_SHAPE, "row_norm_chain: modulation offset %d + D %d exceeds the row stride %ld", off, a2.D, ld);
+  }
   const dim3 grid((unsigned)((a2.rows + 3) / 4));
   ProfScope prof(PROF_ROWNORM, 2.0 * a2.rows * a2.D * 6.0, st);
   dispatch_half(dtype, [&](auto tag) {

@@ -425,13 +425,9 @@ def test_small_m_gemm_rejects_other_shapes(hip, force_tile):
         hip.gemm_bias_act(a, w, None, 0)
 
 
-@pytest.mark.parametrize("dtype", HALF)
-@pytest.mark.parametrize("D", [128, 768, 1024, 1536])
-def test_row_norm_chain_equals_two_row_norms(hip, dtype, D):
-    """Last block's gated norm + residual and the final layer's modulate as one row pass (nova_row_norm_chain) against
-    nova_row_norm twice: identical bits for h and for the stored x_new."""
+def _chain_equals_two_row_norms(hip, dtype, D, in_scale=1.0):
     rows = 203
-    g, x = rnd(rows, D, dtype=dtype, seed=71), rnd(rows, D, dtype=dtype, seed=72)
+    g, x = rnd(rows, D, dtype=dtype, scale=in_scale, seed=71), rnd(rows, D, dtype=dtype, scale=in_scale, seed=72)
     gamma, beta = rnd(D, seed=73) + 1, rnd(D, seed=74)
     mod = rnd(rows, 5 * D, dtype=dtype, scale=0.5, seed=75)
     x_two = hip.row_norm(g, gamma=gamma, beta=beta, mod=mod, gate_off=4 * D, res=x, eps=1e-5)
@@ -446,12 +442,27 @@ def test_row_norm_chain_equals_two_row_norms(hip, dtype, D):
     assert torch.equal(h2, h_two)
 
 
-@pytest.mark.parametrize("rows,D,N", [(1, 768, 768), (37, 768, 768), (256, 768, 768), (300, 1024, 1024), (77, 1024, 2048)])
+CHAIN_WIDTHS = [8, 128, 768, 1024, 1032, 1536, 2048]  # a single lane, one 16-byte chunk over the 2 | 4 chunks-per-lane switch, the full width
+
+
 @pytest.mark.parametrize("dtype", HALF)
-def test_adaln_fc1_fused_equals_two_launches(hip, force_tile, dtype, rows, D, N):
-    """modulate -> fc1 -> SiLU (diffusion_mlp.py:41-47) as ONE launch (LN prologue inside the small-M GEMM) against
-    nova_row_norm followed by the GEMM: identical bits, and both close to fp32 math."""
-    x = rnd(rows, D, dtype=dtype, seed=61)
+@pytest.mark.parametrize("D", CHAIN_WIDTHS)
+def test_row_norm_chain_equals_two_row_norms(hip, dtype, D):
+    """Last block's gated norm + residual and the final layer's modulate as one row pass (nova_row_norm_chain) against
+    nova_row_norm twice: identical bits for h and for the stored x_new."""
+    _chain_equals_two_row_norms(hip, dtype, D)
+
+
+@pytest.mark.parametrize("dtype", HALF)
+@pytest.mark.parametrize("D", CHAIN_WIDTHS)
+def test_row_norm_chain_equals_two_row_norms_on_tiny_rows(hip, dtype, D):
+    """The same with g and x of 1e-3 N(0,1) (the `tiny` family of tests/test_row_contract_cpu.py): the first norm's variance is about 1e-6,
+    so its eps (1e-5, not the second norm's 1e-6) decides rstd, and a chain that hands it the wrong one no longer equals the two launches."""
+    _chain_equals_two_row_norms(hip, dtype, D, in_scale=1e-3)
+
+
+def _adaln_fc1_fused_equals_two_launches(hip, force_tile, dtype, rows, D, N, in_scale=1.0):
+    x = rnd(rows, D, dtype=dtype, scale=in_scale, seed=61)
     mod = rnd(rows, 5 * D, dtype=dtype, scale=0.5, seed=62)
     w, bias = rnd(N, D, dtype=dtype, scale=D ** -0.5, seed=63), rnd(N, seed=64)
     force_tile(16)
@@ -468,6 +479,25 @@ def test_adaln_fc1_fused_equals_two_launches(hip, force_tile, dtype, rows, D, N)
     force_tile(0)
     o32 = hip.adaln_fc1(f32[0], f32[1], D, 3 * D, f32[2], bias, act=2, eps=1e-6)
     assert relerr(o32, torch.nn.functional.silu((ln * (1 + f32[1][:, D:2 * D]) + f32[1][:, 3 * D:4 * D]) @ f32[2].T + bias)) < tol(torch.float32)
+
+
+ADALN_SHAPES = [(1, 768, 768), (37, 768, 768), (256, 768, 768), (300, 1024, 1024), (77, 1024, 2048)]
+
+
+@pytest.mark.parametrize("rows,D,N", ADALN_SHAPES)
+@pytest.mark.parametrize("dtype", HALF)
+def test_adaln_fc1_fused_equals_two_launches(hip, force_tile, dtype, rows, D, N):
+    """modulate -> fc1 -> SiLU (diffusion_mlp.py:41-47) as ONE launch (LN prologue inside the small-M GEMM) against
+    nova_row_norm followed by the GEMM: identical bits, and both close to fp32 math."""
+    _adaln_fc1_fused_equals_two_launches(hip, force_tile, dtype, rows, D, N)
+
+
+@pytest.mark.parametrize("rows,D,N", ADALN_SHAPES)
+@pytest.mark.parametrize("dtype", HALF)
+def test_adaln_fc1_fused_equals_two_launches_on_tiny_rows(hip, force_tile, dtype, rows, D, N):
+    """The same on rows of 1e-3 N(0,1): eps = 1e-6 is as large as the variance, so the LN prologue inside the GEMM and nova_row_norm must
+    agree on it to stay bit-identical."""
+    _adaln_fc1_fused_equals_two_launches(hip, force_tile, dtype, rows, D, N, in_scale=1e-3)
 
 
 @pytest.mark.parametrize("form", TILE256_FORMS)
