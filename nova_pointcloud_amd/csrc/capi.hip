@@ -142,7 +142,8 @@ int nova_gemm_fp8_bias_act(const void* A8, const float* a_scale, const void* W8,
                            void* out, int M, int N, int K, int act, void* stream) {
   NOVA_REQUIRE(M <= 0 || (A8 && a_scale && W8 && w_scale && out), NOVA_ERR_ARG, "gemm_fp8: null pointer");
   NOVA_REQUIRE(act >= NOVA_ACT_NONE && act <= NOVA_ACT_SILU, NOVA_ERR_ARG, "gemm_fp8: bad activation %d", act);
-  return gemm256_fp8_launch(A8, a_scale, W8, w_scale, bias, out, M, N, K, act, (hipStream_t)stream);
+  return gemm256_fp8_launch({.A8 = A8, .sa = a_scale, .W8 = W8, .sw = w_scale, .C = out, .M = M, .N = N, .K = K, .epi = act, .e = epi_bias(bias)},
+                            (hipStream_t)stream);
 }
 
 int nova_qkv_rope(const void* x, const void* Wqkv, const float* bias, const float* rope, void* qkv, int S, int L, int D,
@@ -271,47 +272,97 @@ int nova_head_cfg_euler(const void* h, const void* w, const float* bias, float* 
 }
 
 
-// Block stack of VisionTransformer.forward. With `cache` the k | v rows of every block are appended to that block's
-// cache ([S][cap][2D], `cache_len` rows already valid) and attention runs over cache_len + L keys
-// (vision_transformer.py:55-60, the conditioning encoder of multi-frame generation); without it over the L rows of x.
-static int vit_blocks(const nova_vit_block* blocks, int nblocks, void* x, int S, int L, int D, int heads, int hidden,
-                      const float* rope, int rope_batch, void* ws_qkv, void* ws_a, void* ws_b, void* ws_h, void* cache,
-                      long cap, long cache_len, int dtype, hipStream_t st) {
-  const int M = S * L, hd = D / heads;
-  if (M == 0) return 0;
+// One invocation of the block stack of VisionTransformer.forward, as the three nova_vit_blocks_forward* entries fill it.
+struct VitCall {
+  const nova_vit_block* blocks;
+  const nova_vit_block_fp8* q = nullptr;  // optional: the weights of the three large linears as e4m3 rows (the fp8 stack below; bf16 only)
+  int nblocks;
+  void* x;  // [S * L, D], in place
+  int S, L, D, heads, hidden;
+  const float* rope;
+  int rope_batch;
+  void *ws_qkv, *ws_a, *ws_b, *ws_h;
+  // optional KV cache: the k | v rows of every block are appended to that block's cache ([S][cap][2D], `cache_len` rows already valid) and
+  // attention runs over cache_len + L keys (vision_transformer.py:55-60, the conditioning encoder of multi-frame generation)
+  void* cache = nullptr;
+  long cap = 0, cache_len = 0;
+  // with q: x and the MLP hidden rows as e4m3 bytes with their row scales; h_scale / h_amax [nblocks] select delayed scaling of the hidden rows
+  void *ws_x8 = nullptr, *ws_h8 = nullptr;
+  float *ws_xs = nullptr, *ws_hs = nullptr, *h_scale = nullptr;
+  unsigned* h_amax = nullptr;
+  int dtype;
+  hipStream_t st;
+};
+
+// One of a block's three large linears (fused QKV, fc1, fc2 = 11/12 of its GEMM FLOPs): g.C = epi(in W^T + bias), described by g. The launch
+// follows the data, not the entry point: the MX-fp8 one where the call carries fp8 weights (g.A8, g.W8), else `in` and `w` in c.dtype.
+static int vit_linear(const VitCall& c, const Fp8Gemm& g, const void* in, const void* w) {
+  if (c.q) return gemm256_fp8_launch(g, c.st);
+  if (g.epi == EPI_ROPE) return gemm_qkv_rope(in, w, g.e.bias, c.rope, g.C, c.S, c.L, c.D, c.heads, c.rope_batch, c.dtype, c.st, g.e.q_scale);
+  return gemm_bias_act(in, w, g.e.bias, g.C, g.M, g.N, g.K, g.epi, c.dtype, c.st);
+}
+
+// x = LN(ws_b) * w + b + x, the post-norm residual; with `side8` the new x once more as e4m3 rows, the A operand of the next fp8 linear
+static int vit_post_norm(const VitCall& c, const float* w, const float* b, bool side8) {
+  RowNormArgs n{c.ws_b, c.x, w, b, nullptr, 0, -1, -1, -1, c.x, nullptr, c.S * c.L, c.D, 1e-5f};
+  n.out8 = side8 ? c.ws_x8 : nullptr;
+  n.out8_scale = side8 ? c.ws_xs : nullptr;
+  return row_norm(n, c.dtype, c.st);
+}
+
+// The walk over the blocks, for all three entries. With fp8 weights (BASELINE configs[4]) they were quantised once per output row at pack
+// time and the activations are quantised per row on the fly: the residual stream by the LayerNorm kernel that produces it (fp8 side
+// output), the MLP hidden rows by fc1's epilogue (delayed scaling) or by one quantisation pass. Attention, its out-projection, the
+// LayerNorm statistics and the residual stream stay bf16 / f32.
+static int vit_blocks(const VitCall& c) {
+  const int M = c.S * c.L, D = c.D, hidden = c.hidden, hd = D / c.heads, dtype = c.dtype;
+  hipStream_t st = c.st;
+  if (M == 0 || c.nblocks == 0) return 0;
   const size_t es = esize(dtype);
   const float scale = 1.0f / sqrtf((float)hd);
-  const char* qkv = static_cast<const char*>(ws_qkv);
+  // bf16 / f16: the softmax scale (in the exp2 domain) is folded into q by the QKV epilogue, before the 16-bit rounding
+  // (epi_qkv then scales the q third: scale * log2 e is 1 for no head width the library accepts)
+  const bool pre = dtype_is16(dtype);
+  const float q_scale = pre ? scale * 1.4426950408889634f : 1.0f;
+  const bool delayed = c.h_scale != nullptr;
+  const char* qkv = static_cast<const char*>(c.ws_qkv);
   Walk walk;
-  for (int i = 0; i < nblocks; ++i) {
-    const nova_vit_block& b = blocks[i];
-    // bf16 / f16: the softmax scale (in the exp2 domain) is folded into q by the QKV epilogue, before the 16-bit rounding
-    const bool pre = dtype_is16(dtype);
+  if (c.q) NOVA_TRY(quantize_rows_fp8(c.x, c.ws_x8, c.ws_xs, M, D, st));  // the stack's input rows; later ones come from the LN kernels
+  for (int i = 0; i < c.nblocks; ++i) {
+    const nova_vit_block& b = c.blocks[i];
+    const nova_vit_block_fp8 w = c.q ? c.q[i] : nova_vit_block_fp8{};
     walk.next();
-    NOVA_TRY(gemm_qkv_rope(x, b.qkv_w, b.qkv_b, rope, ws_qkv, S, L, D, heads, rope_batch, dtype, st,
-                           pre ? scale * 1.4426950408889634f : 1.0f));
+    NOVA_TRY(vit_linear(c, {.A8 = c.ws_x8, .sa = c.ws_xs, .W8 = w.qkv_w8, .sw = w.qkv_ws, .C = c.ws_qkv, .M = M, .N = 3 * D, .K = D, .epi = EPI_ROPE,
+                            .e = epi_qkv(b.qkv_b, c.rope, c.L, c.rope_batch, hd, D, q_scale)},
+                        c.x, b.qkv_w));
     walk.next();
-    if (cache) {
-      char* cb = static_cast<char*>(cache) + (size_t)i * S * cap * 2 * D * es;
-      NOVA_TRY(kv_append(ws_qkv, cb, S, L, D, cap, cache_len, dtype, st));
-      NOVA_TRY(attn_fwd(qkv, cb, cb + (size_t)D * es, ws_a, S, heads, L, (int)(cache_len + L), hd, 3L * D, 2L * D, D, scale, dtype,
-                        st, pre, cap * 2L * D));
+    if (c.cache) {
+      char* cb = static_cast<char*>(c.cache) + (size_t)i * c.S * c.cap * 2 * D * es;
+      NOVA_TRY(kv_append(c.ws_qkv, cb, c.S, c.L, D, c.cap, c.cache_len, dtype, st));
+      NOVA_TRY(attn_fwd(qkv, cb, cb + (size_t)D * es, c.ws_a, c.S, c.heads, c.L, (int)(c.cache_len + c.L), hd, 3L * D, 2L * D, D, scale, dtype,
+                        st, pre, c.cap * 2L * D));
     } else {
-      NOVA_TRY(attn_fwd(qkv, qkv + (size_t)D * es, qkv + (size_t)2 * D * es, ws_a, S, heads, L, L, hd, 3L * D, 3L * D, D,
+      NOVA_TRY(attn_fwd(qkv, qkv + (size_t)D * es, qkv + (size_t)2 * D * es, c.ws_a, c.S, c.heads, c.L, c.L, hd, 3L * D, 3L * D, D,
                         scale, dtype, st, pre));
     }
     walk.next();
-    NOVA_TRY(gemm_bias_act(ws_a, b.proj_w, b.proj_b, ws_b, M, D, D, NOVA_ACT_NONE, dtype, st));
-    RowNormArgs n1{ws_b, x, b.norm1_w, b.norm1_b, nullptr, 0, -1, -1, -1, x, nullptr, M, D, 1e-5f};
+    NOVA_TRY(gemm_bias_act(c.ws_a, b.proj_w, b.proj_b, c.ws_b, M, D, D, NOVA_ACT_NONE, dtype, st));
     walk.next();
-    NOVA_TRY(row_norm(n1, dtype, st));
+    NOVA_TRY(vit_post_norm(c, b.norm1_w, b.norm1_b, c.q != nullptr));
     walk.next();
-    NOVA_TRY(gemm_bias_act(x, b.fc1_w, b.fc1_b, ws_h, M, hidden, D, NOVA_ACT_GELU_ERF, dtype, st));
+    // delayed scaling: fc1 writes GELU(.) / h_scale[i] as e4m3 itself and records max |GELU(.)| in h_amax[i], from which the caller sets
+    // the scale of the next call, and fc2 reads one scale for all rows; else fp8 hidden rows take one quantisation pass with a scale each
+    NOVA_TRY(vit_linear(c, {.A8 = c.ws_x8, .sa = c.ws_xs, .W8 = w.fc1_w8, .sw = w.fc1_ws, .C = delayed ? c.ws_h8 : c.ws_h, .M = M, .N = hidden, .K = D,
+                            .epi = delayed ? EPI_GELU_Q8 : EPI_GELU, .e = epi_bias(b.fc1_b), .q8_scale = delayed ? c.h_scale + i : nullptr,
+                            .q8_amax = delayed ? c.h_amax + i : nullptr},
+                        c.x, b.fc1_w));
+    if (c.q && !delayed) NOVA_TRY(quantize_rows_fp8(c.ws_h, c.ws_h8, c.ws_hs, M, hidden, st));
     walk.next();
-    NOVA_TRY(gemm_bias_act(ws_h, b.fc2_w, b.fc2_b, ws_b, M, D, hidden, NOVA_ACT_NONE, dtype, st));
-    RowNormArgs n2{ws_b, x, b.norm2_w, b.norm2_b, nullptr, 0, -1, -1, -1, x, nullptr, M, D, 1e-5f};
+    NOVA_TRY(vit_linear(c, {.A8 = c.ws_h8, .sa = delayed ? c.h_scale + i : c.ws_hs, .sa_scalar = delayed, .W8 = w.fc2_w8, .sw = w.fc2_ws, .C = c.ws_b,
+                            .M = M, .N = D, .K = hidden, .epi = EPI_NONE, .e = epi_bias(b.fc2_b)},
+                        c.ws_h, b.fc2_w));
     walk.next();
-    NOVA_TRY(row_norm(n2, dtype, st));
+    NOVA_TRY(vit_post_norm(c, b.norm2_w, b.norm2_b, c.q && i + 1 < c.nblocks));  // fp8: the next block's QKV input
   }
   return 0;
 }
@@ -322,8 +373,8 @@ int nova_vit_blocks_forward(const nova_vit_block* blocks, int nblocks, void* x, 
   NOVA_REQUIRE(!bad_dtype(dtype), NOVA_ERR_ARG, "vit_blocks: bad dtype %d", dtype);
   NOVA_REQUIRE(nblocks == 0 || (blocks && x && ws_qkv && ws_a && ws_b && ws_h), NOVA_ERR_ARG, "vit_blocks: null pointer");
   NOVA_REQUIRE(heads > 0 && D % heads == 0, NOVA_ERR_SHAPE, "vit_blocks: D %% heads != 0");
-  return vit_blocks(blocks, nblocks, x, S, L, D, heads, hidden, rope, rope_batch, ws_qkv, ws_a, ws_b, ws_h, nullptr, 0, 0, dtype,
-                    (hipStream_t)stream);
+  return vit_blocks({.blocks = blocks, .nblocks = nblocks, .x = x, .S = S, .L = L, .D = D, .heads = heads, .hidden = hidden, .rope = rope,
+                     .rope_batch = rope_batch, .ws_qkv = ws_qkv, .ws_a = ws_a, .ws_b = ws_b, .ws_h = ws_h, .dtype = dtype, .st = (hipStream_t)stream});
 }
 
 int nova_row_norm_fp8(const void* in, void* out, const float* gamma, const float* beta, const void* res, void* out8, float* out8_scale,
@@ -338,22 +389,21 @@ int nova_row_norm_fp8(const void* in, void* out, const float* gamma, const float
 int nova_gemm_fp8_gelu_q8(const void* A8, const float* a_scale, const void* W8, const float* w_scale, const float* bias, void* out8,
                           int M, int N, int K, const float* out_scale, unsigned* out_amax, void* stream) {
   NOVA_REQUIRE(M <= 0 || (A8 && a_scale && W8 && w_scale && out8 && out_scale && out_amax), NOVA_ERR_ARG, "gemm_fp8_gelu_q8: null pointer");
-  return gemm256_fp8_launch(A8, a_scale, W8, w_scale, bias, out8, M, N, K, NOVA_EPI_GELU_Q8, (hipStream_t)stream, nullptr, 1, 1, 2, 0, 1.0f,
-                            0, 0, out_scale, out_amax);
+  return gemm256_fp8_launch({.A8 = A8, .sa = a_scale, .W8 = W8, .sw = w_scale, .C = out8, .M = M, .N = N, .K = K, .epi = EPI_GELU_Q8,
+                             .e = epi_bias(bias), .q8_scale = out_scale, .q8_amax = out_amax},
+                            (hipStream_t)stream);
 }
 
 int nova_qkv_rope_fp8(const void* x8, const float* x_scale, const void* w8, const float* w_scale, const float* bias, const float* rope,
                       void* qkv, int S, int L, int D, int heads, int rope_batch, float q_scale, void* stream) {
   NOVA_REQUIRE(S * L == 0 || (x8 && x_scale && w8 && w_scale && qkv), NOVA_ERR_ARG, "qkv_rope_fp8: null pointer");
   NOVA_REQUIRE(heads > 0 && D % heads == 0, NOVA_ERR_SHAPE, "qkv_rope_fp8: D %% heads != 0");
-  return gemm256_fp8_launch(x8, x_scale, w8, w_scale, bias, qkv, S * L, 3 * D, D, 3, (hipStream_t)stream, rope, L, rope_batch, D / heads,
-                            rope ? 2 * D : 0, q_scale, q_scale != 1.0f ? D : 0);
+  return gemm256_fp8_launch({.A8 = x8, .sa = x_scale, .W8 = w8, .sw = w_scale, .C = qkv, .M = S * L, .N = 3 * D, .K = D, .epi = EPI_ROPE,
+                             .e = epi_qkv(bias, rope, L, rope_batch, D / heads, D, q_scale)},
+                            (hipStream_t)stream);
 }
 
-// The block stack with the three large GEMMs of every block (fused QKV, fc1, fc2 = 11/12 of a block's GEMM FLOPs) on the
-// MX-fp8 MFMA path (BASELINE configs[4]): weights quantised once per output row at pack time, activations quantised per
-// row on the fly - the residual stream by the LayerNorm kernel that produces it (fp8 side output), the MLP hidden rows by
-// one quantisation pass. Attention, its out-projection, LayerNorm statistics and the residual stream stay bf16 / f32.
+// The block stack with the three large linears of every block on the MX-fp8 MFMA path (vit_blocks above)
 int nova_vit_blocks_forward_fp8(const nova_vit_block* blocks, const nova_vit_block_fp8* q, int nblocks, void* x, int S, int L, int D,
                                 int heads, int hidden, const float* rope, int rope_batch, void* ws_qkv, void* ws_a, void* ws_b,
                                 void* ws_h, void* ws_x8, float* ws_xs, void* ws_h8, float* ws_hs, float* h_scale, unsigned* h_amax,
@@ -364,53 +414,9 @@ int nova_vit_blocks_forward_fp8(const nova_vit_block* blocks, const nova_vit_blo
   NOVA_REQUIRE(heads > 0 && D % heads == 0, NOVA_ERR_SHAPE, "vit_blocks_fp8: D %% heads != 0");
   NOVA_REQUIRE(D % 256 == 0 && hidden % 256 == 0, NOVA_ERR_SHAPE, "vit_blocks_fp8: D and hidden must be multiples of 256");
   NOVA_REQUIRE(!rope || L >= 16, NOVA_ERR_SHAPE, "vit_blocks_fp8: L >= 16 with RoPE");
-  hipStream_t st = (hipStream_t)stream;
-  const int M = S * L, hd = D / heads;
-  if (M == 0 || nblocks == 0) return 0;
-  const float scale = 1.0f / sqrtf((float)hd);
-  const char* qkv = static_cast<const char*>(ws_qkv);
-  Walk walk;
-  NOVA_TRY(quantize_rows_fp8(x, ws_x8, ws_xs, M, D, st));  // the stack's input rows; later ones come from the LN kernels
-  for (int i = 0; i < nblocks; ++i) {
-    const nova_vit_block& b = blocks[i];
-    const nova_vit_block_fp8& w = q[i];
-    walk.next();
-    NOVA_TRY(gemm256_fp8_launch(ws_x8, ws_xs, w.qkv_w8, w.qkv_ws, b.qkv_b, ws_qkv, M, 3 * D, D, 3 /* RoPE + q-scale */, st, rope, L,
-                                rope_batch, hd, rope ? 2 * D : 0, scale * 1.4426950408889634f, D));
-    walk.next();
-    NOVA_TRY(attn_fwd(qkv, qkv + (size_t)D * 2, qkv + (size_t)2 * D * 2, ws_a, S, heads, L, L, hd, 3L * D, 3L * D, D, scale, NOVA_BF16,
-                      st, true));
-    walk.next();
-    NOVA_TRY(gemm_bias_act(ws_a, b.proj_w, b.proj_b, ws_b, M, D, D, NOVA_ACT_NONE, NOVA_BF16, st));
-    RowNormArgs n1{ws_b, x, b.norm1_w, b.norm1_b, nullptr, 0, -1, -1, -1, x, nullptr, M, D, 1e-5f};
-    n1.out8 = ws_x8;
-    n1.out8_scale = ws_xs;
-    walk.next();
-    NOVA_TRY(row_norm(n1, NOVA_BF16, st));
-    walk.next();
-    if (h_scale) {
-      // delayed scaling: fc1 writes GELU(.) / h_scale[i] as e4m3 itself and records max |GELU(.)| in h_amax[i], from which the
-      // caller sets the scale of the next call; fc2 reads one scale for all rows
-      NOVA_TRY(gemm256_fp8_launch(ws_x8, ws_xs, w.fc1_w8, w.fc1_ws, b.fc1_b, ws_h8, M, hidden, D, NOVA_EPI_GELU_Q8, st, nullptr, 1, 1, 2, 0,
-                                  1.0f, 0, 0, h_scale + i, h_amax + i));
-      walk.next();
-      NOVA_TRY(gemm256_fp8_launch(ws_h8, h_scale + i, w.fc2_w8, w.fc2_ws, b.fc2_b, ws_b, M, D, hidden, NOVA_ACT_NONE, st, nullptr, 1, 1, 2, 0,
-                                  1.0f, 0, 1));
-    } else {
-      NOVA_TRY(gemm256_fp8_launch(ws_x8, ws_xs, w.fc1_w8, w.fc1_ws, b.fc1_b, ws_h, M, hidden, D, NOVA_ACT_GELU_ERF, st));
-      NOVA_TRY(quantize_rows_fp8(ws_h, ws_h8, ws_hs, M, hidden, st));
-      walk.next();
-      NOVA_TRY(gemm256_fp8_launch(ws_h8, ws_hs, w.fc2_w8, w.fc2_ws, b.fc2_b, ws_b, M, D, hidden, NOVA_ACT_NONE, st));
-    }
-    RowNormArgs n2{ws_b, x, b.norm2_w, b.norm2_b, nullptr, 0, -1, -1, -1, x, nullptr, M, D, 1e-5f};
-    if (i + 1 < nblocks) {  // the next block's QKV input
-      n2.out8 = ws_x8;
-      n2.out8_scale = ws_xs;
-    }
-    walk.next();
-    NOVA_TRY(row_norm(n2, NOVA_BF16, st));
-  }
-  return 0;
+  return vit_blocks({.blocks = blocks, .q = q, .nblocks = nblocks, .x = x, .S = S, .L = L, .D = D, .heads = heads, .hidden = hidden, .rope = rope,
+                     .rope_batch = rope_batch, .ws_qkv = ws_qkv, .ws_a = ws_a, .ws_b = ws_b, .ws_h = ws_h, .ws_x8 = ws_x8, .ws_h8 = ws_h8,
+                     .ws_xs = ws_xs, .ws_hs = ws_hs, .h_scale = h_scale, .h_amax = h_amax, .dtype = NOVA_BF16, .st = (hipStream_t)stream});
 }
 
 int nova_vit_blocks_forward_kv(const nova_vit_block* blocks, int nblocks, void* x, int S, int L, int D, int heads,
@@ -421,8 +427,9 @@ int nova_vit_blocks_forward_kv(const nova_vit_block* blocks, int nblocks, void* 
   NOVA_REQUIRE(heads > 0 && D % heads == 0, NOVA_ERR_SHAPE, "vit_blocks_kv: D %% heads != 0");
   NOVA_REQUIRE(cache_len >= 0 && cache_len + L <= cache_cap, NOVA_ERR_SHAPE, "vit_blocks_kv: %ld cached + %d new rows exceed the capacity %ld",
                cache_len, L, cache_cap);
-  return vit_blocks(blocks, nblocks, x, S, L, D, heads, hidden, rope, rope_batch, ws_qkv, ws_a, ws_b, ws_h, kv_cache, cache_cap,
-                    cache_len, dtype, (hipStream_t)stream);
+  return vit_blocks({.blocks = blocks, .nblocks = nblocks, .x = x, .S = S, .L = L, .D = D, .heads = heads, .hidden = hidden, .rope = rope,
+                     .rope_batch = rope_batch, .ws_qkv = ws_qkv, .ws_a = ws_a, .ws_b = ws_b, .ws_h = ws_h, .cache = kv_cache, .cap = cache_cap,
+                     .cache_len = cache_len, .dtype = dtype, .st = (hipStream_t)stream});
 }
 
 int nova_modulate_rows(const void* x, const void* mod, void* out, long rows, int D, int dtype, void* stream) {

@@ -299,7 +299,7 @@ static int launch_gemm(const void* A, const void* W, void* C, int M, int N, int 
 
 int gemm_bias_act(const void* A, const void* W, const float* bias, void* out, int M, int N, int K, int act,
                   int dtype, hipStream_t st) {
-  GemmEpi e{bias, nullptr, 1, 1, 2, 0, 1.0f, 0};
+  const GemmEpi e = epi_bias(bias);
   if (act < 0 || act > 2) return set_error(NOVA_ERR_ARG, "gemm: unknown activation %d", act);
   if (dtype_is16(dtype) && (g_force_tile == 16 || (g_force_tile == 0 && skinny_gemm_fits(M, N, K, false))))
     return skinny_gemm(A, W, bias, out, M, N, K, act, nullptr, dtype, st);
@@ -324,7 +324,7 @@ int gemm_qkv_rope(const void* x, const void* Wqkv, const float* bias, const floa
   if (heads <= 0 || D % heads != 0 || hd % 4 != 0) return set_error(NOVA_ERR_SHAPE, "qkv_rope: bad heads/D");
   const int epi = (rope || q_scale != 1.0f) ? EPI_ROPE : EPI_NONE;
   if (rope && rope_batch <= 0) return set_error(NOVA_ERR_ARG, "qkv_rope: rope_batch must be > 0");
-  GemmEpi e{bias, rope, L, rope ? rope_batch : 1, hd, rope ? 2 * D : 0, q_scale, q_scale != 1.0f ? D : 0};
+  const GemmEpi e = epi_qkv(bias, rope, L, rope_batch, hd, D, q_scale);
   return dispatch_dtype(dtype, [&](auto tag) { return launch_gemm<decltype(tag)>(x, Wqkv, qkv, S * L, 3 * D, D, epi, e, st); });
 }
 

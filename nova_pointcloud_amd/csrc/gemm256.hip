@@ -1154,20 +1154,20 @@ static int launch256p(const T* a, const T* w, typename OutOf<T>::type* c, int M,
 // MX-fp8 operands (OCP e4m3 bytes, K % 128 == 0), bf16 result; persistent kernel only. Internal entry for capi.hip.
 // epi EPI_ROPE: the fused-QKV epilogue (rotation of the first rope_cols columns with the [rope_batch, L, hd/2, 2] table,
 // q_scale on the first q_cols columns), applied after the dequantisation scales and the bias.
-int gemm256_fp8_launch(const void* A8, const float* sa, const void* W8, const float* sw, const float* bias, void* C, int M,
-                       int N, int K, int epi, hipStream_t st, const float* rope, int L, int rope_batch, int hd, int rope_cols,
-                       float q_scale, int q_cols, int sa_scalar, const float* q8_scale, unsigned* q8_amax) {
+int gemm256_fp8_launch(const Fp8Gemm& g, hipStream_t st) {
+  const int M = g.M, N = g.N, K = g.K;
+  const GemmEpi& x = g.e;
   if (M <= 0) return 0;
   if (N % 256 != 0 || K % 128 != 0 || K <= 0) return set_error(NOVA_ERR_SHAPE, "gemm_fp8: need N %% 256 == 0 and K %% 128 == 0 (got N=%d K=%d)", N, K);
-  if (epi == EPI_ROPE && (rope_cols % 256 || q_cols % 256 || (rope && (L < 16 || rope_batch <= 0 || hd <= 0))))
+  if (g.epi == EPI_ROPE && (x.rope_cols % 256 || x.q_cols % 256 || (x.rope && (x.L < 16 || x.rope_batch <= 0 || x.hd <= 0))))
     return set_error(NOVA_ERR_SHAPE, "gemm_fp8: RoPE epilogue needs rope_cols, q_cols %% 256 == 0 and L >= 16");
-  GemmEpi256 e{{bias, rope, rope ? L : 1, rope ? rope_batch : 1, rope ? hd : 2, rope ? rope_cols : 0, q_scale, q_cols}, g_gm256,
-               walk_is_reverse() ? 1 : 0, sa, sw, 0};
-  e.sa_scalar = sa_scalar;
-  e.q8_scale = q8_scale;
-  e.q8_amax = q8_amax;
-  if (epi == EPI_GELU_Q8 && (!q8_scale || !q8_amax)) return set_error(NOVA_ERR_ARG, "gemm_fp8: the e4m3-output epilogue needs a scale and an amax word");
-  return launch256p<fp8_t>(static_cast<const fp8_t*>(A8), static_cast<const fp8_t*>(W8), static_cast<bf16_t*>(C), M, N, K, epi, e, st);
+  GemmEpi256 e{{x.bias, x.rope, x.rope ? x.L : 1, x.rope ? x.rope_batch : 1, x.rope ? x.hd : 2, x.rope ? x.rope_cols : 0, x.q_scale, x.q_cols}, g_gm256,
+               walk_is_reverse() ? 1 : 0, g.sa, g.sw, 0};
+  e.sa_scalar = g.sa_scalar;
+  e.q8_scale = g.q8_scale;
+  e.q8_amax = g.q8_amax;
+  if (g.epi == EPI_GELU_Q8 && (!g.q8_scale || !g.q8_amax)) return set_error(NOVA_ERR_ARG, "gemm_fp8: the e4m3-output epilogue needs a scale and an amax word");
+  return launch256p<fp8_t>(static_cast<const fp8_t*>(g.A8), static_cast<const fp8_t*>(g.W8), static_cast<bf16_t*>(g.C), M, N, K, g.epi, e, st);
 }
 
 template <typename T>

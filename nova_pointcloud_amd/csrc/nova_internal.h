@@ -57,11 +57,15 @@ struct GemmEpi {
   float q_scale;         // columns [0, q_cols) are multiplied by this after rotation (softmax scale folded into q)
   int q_cols;
 };
+inline GemmEpi epi_bias(const float* bias) { return {bias, nullptr, 1, 1, 2, 0, 1.0f, 0}; }
+// the fused QKV projection [.., 3D]: q and k thirds rotated where there is a table, the q third scaled where q_scale says anything
+inline GemmEpi epi_qkv(const float* bias, const float* rope, int L, int rope_batch, int hd, int D, float q_scale) {
+  return {bias, rope, L, rope ? rope_batch : 1, hd, rope ? 2 * D : 0, q_scale, q_scale != 1.0f ? D : 0};
+}
 // EPI_NONE .. EPI_SILU are the public activation codes (NOVA_ACT_*). EPI_GELU_Q8 (fp8 operands only, gemm256.hip): GELU, then the
 // result is written as OCP e4m3 bytes, value / *q8_scale saturated at +-448, instead of bf16 - the A operand of the next fp8 GEMM
 // without a quantisation pass ("delayed scaling": the caller derives the next call's scale from q8_amax).
 enum { EPI_NONE = 0, EPI_GELU = 1, EPI_SILU = 2, EPI_ROPE = 3, EPI_GELU_Q8 = 5 };
-constexpr int NOVA_EPI_GELU_Q8 = EPI_GELU_Q8;  // (the name capi.hip calls it by)
 // epilogue code -> compile-time tag, for the four epilogues every structure and storage type has: f(std::integral_constant<int, EPI_x>{})
 // launches; returns 0, or the error for any other code
 template <typename F> inline int dispatch_epi(int epi, F&& f) {
@@ -176,10 +180,21 @@ int build_sequence(const void* prefix, long prefix_seq_rows, const void* tokens,
 int scatter_tokens(const void* x1, const long long* ids, void* x2, int S, int B, int Lp, int N, int n_prev, int D,
                    int dtype, hipStream_t st);
 int quantize_rows_fp8(const void* x, void* out, float* scale, long rows, int D, hipStream_t st);
-int gemm256_fp8_launch(const void* A8, const float* sa, const void* W8, const float* sw, const float* bias, void* C, int M,
-                       int N, int K, int epi, hipStream_t st, const float* rope = nullptr, int L = 1, int rope_batch = 1,
-                       int hd = 2, int rope_cols = 0, float q_scale = 1.0f, int q_cols = 0, int sa_scalar = 0,
-                       const float* q8_scale = nullptr, unsigned* q8_amax = nullptr);
+// gemm256.hip: C = epi((A8 W8^T) * sa[m] * sw[n] + bias) on MX-fp8 operands (OCP e4m3 bytes); C is bf16, or e4m3 bytes with EPI_GELU_Q8
+struct Fp8Gemm {
+  const void* A8;       // [M, K]
+  const float* sa;      // [M] row scales of A8, or one scale for all rows with sa_scalar
+  int sa_scalar = 0;
+  const void* W8;       // [N, K]
+  const float* sw;      // [N]
+  void* C;              // [M, N]
+  int M, N, K;
+  int epi;              // EPI_*
+  GemmEpi e;
+  const float* q8_scale = nullptr;  // EPI_GELU_Q8 only: the scale the e4m3 result is divided by ...
+  unsigned* q8_amax = nullptr;      // ... and the word that takes max |GELU(.)| (float bits)
+};
+int gemm256_fp8_launch(const Fp8Gemm& g, hipStream_t st);
 int silu_add_rows(const void* a, const void* rowvec, void* out, long rows, int D, int dtype, hipStream_t st);
 int silu_add_steps(const void* a, const void* vecs, void* out, long rows, int nvec, int D, int dtype, hipStream_t st);
 int timestep_freq(const float* t, const float* freq, void* out, int n, int freq_dim, int dtype, hipStream_t st);

@@ -42,7 +42,6 @@ template <> struct Vec4<f16_t> : Vec4Half<f16_t> {};
 template <typename T, int NIT, bool HAS_RES, bool HAS_MOD>
 __global__ __launch_bounds__(256) void row_norm_kernel(RowNormArgs a) {
   using C = Chunk<T>;
-  constexpr int NV = C::N / 4;
   const int lane = threadIdx.x & 63;
   // XCD x walks one contiguous eighth of the rows, front to back or back to front (xcd_remap_dir, common.h)
   const long row = (long)xcd_remap_dir(blockIdx.x, gridDim.x, a.rev != 0) * 4 + (threadIdx.x >> 6);
@@ -50,44 +49,19 @@ __global__ __launch_bounds__(256) void row_norm_kernel(RowNormArgs a) {
   C x[NIT];  // the finished row (rownorm.h: all of a row's HBM traffic is in flight before the two wave reductions)
   row_norm_compute<T, NIT, HAS_RES, HAS_MOD>(a, row, lane, x);
   T* out = static_cast<T*>(a.out) + row * a.D;
-  const bool q8 = sizeof(T) == 2 && a.out8 != nullptr;  // also emit the row as e4m3 + scale (what the next fp8 GEMM reads)
-  float amax = 0.f;
 #pragma unroll
   for (int it = 0; it < NIT; ++it) {
     const int d = (it * 64 + lane) * C::N;
-    if (d < a.D) {
-      x[it].store(out + d);
-      if (q8) {  // quantise what was STORED (the bf16-rounded row), so the fp8 copy equals quantize_rows_fp8(out)
-        x[it] = x[it].rounded();
-#pragma unroll
-        for (int k = 0; k < NV; ++k)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) amax = fmaxf(amax, fabsf(x[it].v[k][j]));
-      }
-    }
+    if (d < a.D) x[it].store(out + d);
   }
-  if constexpr (sizeof(T) == 2) {
-    if (q8) {
-      amax = wave_max(amax);
-      const float sc = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
-      const float inv = 1.0f / sc;
-      if (lane == 0) a.out8_scale[row] = sc;
-      uint8_t* o8 = static_cast<uint8_t*>(a.out8) + row * a.D;
+  if constexpr (std::is_same_v<T, bf16_t>) {  // row_norm() admits the side output for bf16 rows only
+    // also emit the row as e4m3 + scale (what the next fp8 GEMM reads): quantise what was STORED (the bf16-rounded row), so the fp8
+    // copy equals quantize_rows_fp8(out)
+    if (a.out8) {
 #pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-        const int d = (it * 64 + lane) * C::N;
-        if (d < a.D) {
-          u2v o;
-#pragma unroll
-          for (int k = 0; k < 2; ++k) {
-            int w = 0;
-            w = __builtin_amdgcn_cvt_pk_fp8_f32(x[it].v[k % NV][0] * inv, x[it].v[k % NV][1] * inv, w, false);
-            w = __builtin_amdgcn_cvt_pk_fp8_f32(x[it].v[k % NV][2] * inv, x[it].v[k % NV][3] * inv, w, true);
-            o[k] = (uint32_t)w;
-          }
-          *reinterpret_cast<u2v*>(o8 + d) = o;
-        }
-      }
+      for (int it = 0; it < NIT; ++it)
+        if ((it * 64 + lane) * C::N < a.D) x[it] = x[it].rounded();
+      quantize_row_fp8<NIT>(x, a.D, lane, static_cast<uint8_t*>(a.out8) + row * a.D, a.out8_scale + row);
     }
   }
 }
@@ -359,44 +333,12 @@ __global__ __launch_bounds__(256) void silu_add_rows_kernel(const T* __restrict_
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const bf16_t* __restrict__ x, uint8_t* __restrict__ out,
                                                                 float* __restrict__ scale, long rows, int D) {
-  using C = Chunk<bf16_t>;
-  constexpr int NIT = 16;
   const int lane = threadIdx.x & 63;
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const bf16_t* in = x + row * D;
-  C v[NIT];
-  float amax = 0.f;
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int d = (it * 64 + lane) * 8;
-    if (d < D) {
-      v[it] = C::load(in + d);
-#pragma unroll
-      for (int k = 0; k < 2; ++k)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) amax = fmaxf(amax, fabsf(v[it].v[k][j]));
-    }
-  }
-  amax = wave_max(amax);
-  const float sc = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
-  const float inv = 1.0f / sc;
-  if (lane == 0) scale[row] = sc;
-#pragma unroll
-  for (int it = 0; it < NIT; ++it) {
-    const int d = (it * 64 + lane) * 8;
-    if (d < D) {
-      u2v o;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        int w = 0;
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(v[it].v[k][0] * inv, v[it].v[k][1] * inv, w, false);
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(v[it].v[k][2] * inv, v[it].v[k][3] * inv, w, true);
-        o[k] = (uint32_t)w;
-      }
-      *reinterpret_cast<u2v*>(out + row * D + d) = o;
-    }
-  }
+  Chunk<bf16_t> v[16];  // D <= 8192
+  quantize_row_fp8<16>(v, D, lane, out + row * D, scale + row, [&](int d) { return Chunk<bf16_t>::load(in + d); });
 }
 
 int quantize_rows_fp8(const void* x, void* out, float* scale, long rows, int D, hipStream_t st) {

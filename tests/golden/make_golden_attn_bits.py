@@ -4,8 +4,9 @@
 
 tests/test_gpu_attn_bits.py then asks the current build for the same bits. The file attn_fwd_bits.json holds no arrays:
 per case the SHA-256 of every input (seeded CPU generators; a drift of the generator then shows as an input mismatch, not
-as a kernel failure) and of every output buffer, padding included. Every case is S = 2, heads = 2; see CASES for what each
-one calls. Shapes: (Lq, Lk) over one exact tile, ragged last tiles, Lk < 64 and Lq across the 128- and 256-row workgroup
+as a kernel failure) and of every output buffer, padding included. Every case is S = 2, and heads = 2 unless it says otherwise;
+see CASES for what each one calls. The vit* cases pin whole block stacks (capi.hip: plain, fp8 in both hidden-row modes, KV-cached),
+the walk direction of every launch included. Attention shapes: (Lq, Lk) over one exact tile, ragged last tiles, Lk < 64 and Lq across the 128- and 256-row workgroup
 edges; for Lk >= 200 two late spike keys make the running max jump after tile 0 (the deferred-rescale branch, which in
 variant 5 also rescales the pending P)."""
 import argparse
@@ -47,6 +48,11 @@ def _cases():
             c[f"lse_masked/hd{hd}/{L}"] = ("lse", dict(hd=hd, variant=-1, L=L, prefix=prefix, frame=frame))
     # the reverse walk (rev = 1) of the workgroup decode: the block composite alternates the direction launch by launch
     c["vit_blocks/bf16/D128/L200"] = ("vit", dict(nblocks=2, D=128, L=200))
+    # the fp8 stack, delayed and row-scaled hidden rows: 342 rows = two 256-row tiles, the last ragged; 2 x 7 walked launches
+    for mode in ("delayed", "rowscaled"):
+        c[f"vit_fp8/{mode}/D256/L171"] = ("vit", dict(nblocks=2, D=256, L=171, heads=4, rope_batch=2, mode=f"fp8_{mode}"))
+    # the 16-bit KV stack: q pre-scaled by the QKV epilogue, keys read from the cache with its sequence stride, two chunks
+    c["vit_kv/bf16/D128"] = ("vit", dict(nblocks=2, D=128, L=0, heads=2, rope_batch=2, mode="kv", chunks=(37, 64), cap=160))
     return c
 
 
@@ -158,7 +164,18 @@ def run_lse(lib, name, hd, variant, L, prefix, frame):
 BLOCK_KEYS = ("qkv_w", "qkv_b", "proj_w", "proj_b", "norm1_w", "norm1_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "norm2_w", "norm2_b")
 
 
-def run_vit(lib, name, nblocks, D, L):
+FP8_KEYS = ("qkv_w", "fc1_w", "fc2_w")  # the three linears nova_vit_blocks_forward_fp8 reads as e4m3 rows
+
+
+def rope_rows(g, batch, L, hd):
+    """A [batch, L, hd/2, 2] (cos, sin) table of seeded angles."""
+    a = torch.rand(batch, L, hd // 2, generator=g) * 6.283185307179586
+    return torch.stack([a.cos(), a.sin()], -1).contiguous()
+
+
+def run_vit(lib, name, nblocks, D, L, heads=HEADS, rope_batch=0, mode="plain", chunks=(), cap=0):
+    """mode "plain": nova_vit_blocks_forward on L rows; "fp8_delayed" / "fp8_rowscaled": nova_vit_blocks_forward_fp8 on L rows;
+    "kv": nova_vit_blocks_forward_kv, one call per entry of `chunks` (rows) over a cache of `cap` rows. rope_batch 0 = no table."""
     from nova_pointcloud_amd import hip
 
     g = torch.Generator().manual_seed(seed_of(name))
@@ -178,13 +195,58 @@ def run_vit(lib, name, nblocks, D, L):
             keep.append(w.cuda())
             ptrs.append(keep[-1].data_ptr())
         arr[b] = hip.VitBlock(*ptrs)
+    def table(key, rows):
+        if not rope_batch:
+            return None
+        ins[key] = rope_rows(g, rope_batch, rows, D // heads)
+        keep.append(ins[key].cuda())
+        return keep[-1].data_ptr()
+
+    def filled(*shape, dtype):  # an output buffer whose untouched bytes hash the same
+        return torch.full(shape, SENTINEL if dtype.is_floating_point else 0xFD, dtype=dtype, device="cuda")
+
+    if mode == "kv":
+        cache = filled(nblocks, S, cap, 2 * D, dtype=dt)
+        outs, done = {"cache": cache}, 0
+        for c, rows in enumerate(chunks):
+            ins[f"x/chunk{c}"] = torch.randn(S * rows, D, generator=g).to(dt)
+            xd = ins[f"x/chunk{c}"].cuda()
+            ws = [torch.empty(S * rows, n, dtype=dt, device="cuda") for n in (3 * D, D, D, hidden)]
+            call(lib, "nova_vit_blocks_forward_kv", arr, nblocks, xd.data_ptr(), S, rows, D, heads, hidden, table(f"rope/chunk{c}", rows), rope_batch or 1,
+                 cache.data_ptr(), cap, done, *[w.data_ptr() for w in ws], hip.dtype_code(dt), stream())
+            outs[f"x/chunk{c}"] = xd
+            done += rows
+        return ins, outs
     x = torch.randn(S * L, D, generator=g).to(dt)
     ins["x"] = x
     xd = x.cuda()
     ws = [torch.empty(S * L, n, dtype=dt, device="cuda") for n in (3 * D, D, D, hidden)]
-    call(lib, "nova_vit_blocks_forward", arr, nblocks, xd.data_ptr(), S, L, D, HEADS, hidden, None, 1, *[w.data_ptr() for w in ws],
-         hip.dtype_code(dt), stream())
-    return ins, {"x": xd}
+    if mode == "plain":
+        call(lib, "nova_vit_blocks_forward", arr, nblocks, xd.data_ptr(), S, L, D, heads, hidden, table("rope", L), rope_batch or 1,
+             *[w.data_ptr() for w in ws], hip.dtype_code(dt), stream())
+        return ins, {"x": xd}
+    # fp8: the weights of the three large linears quantised per output row by the same library, and hashed among the inputs
+    arr8 = (hip.VitBlockFp8 * nblocks)()
+    for b in range(nblocks):
+        ptrs = []
+        for key in FP8_KEYS:
+            w = keep[b * len(BLOCK_KEYS) + BLOCK_KEYS.index(key)]
+            w8, wsc = torch.empty(w.shape, dtype=torch.uint8, device="cuda"), torch.empty(w.shape[0], device="cuda")
+            call(lib, "nova_quantize_rows_fp8", w.data_ptr(), w8.data_ptr(), wsc.data_ptr(), w.shape[0], w.shape[1], stream())
+            ins[f"block{b}/{key}8"], ins[f"block{b}/{key}s"] = w8, wsc
+            ptrs += [w8.data_ptr(), wsc.data_ptr()]
+        arr8[b] = hip.VitBlockFp8(*ptrs)
+    rope = table("rope", L)
+    outs = {"x": xd, "ws_x8": filled(S * L, D, dtype=torch.uint8), "ws_xs": filled(S * L, dtype=torch.float32),
+            "ws_h8": filled(S * L, hidden, dtype=torch.uint8), "ws_hs": filled(S * L, dtype=torch.float32)}
+    h_scale = h_amax = None
+    if mode == "fp8_delayed":  # both are outputs: the scale is read, the amax word recorded per block
+        outs["h_scale"] = torch.full((nblocks,), 64.0 / 448.0, dtype=torch.float32, device="cuda")
+        outs["h_amax"] = torch.zeros(nblocks, dtype=torch.int32, device="cuda")
+        h_scale, h_amax = outs["h_scale"].data_ptr(), outs["h_amax"].data_ptr()
+    call(lib, "nova_vit_blocks_forward_fp8", arr, arr8, nblocks, xd.data_ptr(), S, L, D, heads, hidden, rope, rope_batch or 1,
+         *[w.data_ptr() for w in ws], *[outs[k].data_ptr() for k in ("ws_x8", "ws_xs", "ws_h8", "ws_hs")], h_scale, h_amax, stream())
+    return ins, outs
 
 
 def run_case(name, lib):

@@ -2,7 +2,8 @@
 in tests/golden/make_golden_attn_bits.py's CASES must hash to what tests/golden/attn_fwd_bits.json records. The fixture
 was written by that generator on an MI355X from the library built at the commit it names (meta.commit); it holds SHA-256
 digests only, of the inputs too, so that a drift of the seeded CPU generators shows as an input mismatch rather than as a
-kernel failure.
+kernel failure. The generator's vit* cases pin whole block stacks the same way (csrc/capi.hip: the plain, the fp8 and the
+KV-cached stack, each launch's walk direction and arguments included).
 
 The recorded bits pin the PRESENT summation order of the kernels: the K/V tile order, the deferred rescale, the MFMA
 contraction order and the row-sum form of each structure. A pull request that changes an order on purpose regenerates the

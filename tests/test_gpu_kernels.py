@@ -544,7 +544,7 @@ def _dequant(q, scale):
     return q.view(torch.float8_e4m3fn).float() * scale[:, None]
 
 
-@pytest.mark.parametrize("rows,D", [(1, 128), (37, 1024), (513, 1536), (4096, 4096)])
+@pytest.mark.parametrize("rows,D", [(1, 128), (37, 1024), (513, 1536), (4096, 4096), (3, 8192), (5, 8)])  # the cap (all 16 chunks live); one lane holds the row
 def test_quantize_rows_fp8(hip, rows, D):
     x = rnd(rows, D, dtype=torch.bfloat16, seed=61)
     x[0, :] = 0 if rows > 1 else x[0, :]  # an all-zero row must not divide by zero

@@ -90,4 +90,7 @@ for tag, N, call in (("fp8 fc1 + GELU 163840 x 4096 x 1024", 4 * D, "gemm"), ("f
         ab(tag, lambda lib: lambda: lib.nova_gemm_fp8_bias_act(x8.data_ptr(), xs.data_ptr(), w8.data_ptr(), ws.data_ptr(), b_.data_ptr(), o_.data_ptr(), S * L, N, D, 1, st), 2.0 * S * L * N * D)
     else:
         ab(tag, lambda lib: lambda: lib.nova_qkv_rope_fp8(x8.data_ptr(), xs.data_ptr(), w8.data_ptr(), ws.data_ptr(), b_.data_ptr(), rope.data_ptr(), o_.data_ptr(), S, L, D, heads, 2, 1.0, st), 2.0 * S * L * N * D)
+# the two row kernels that share the fp8 row quantiser (rownorm.h): the quantisation pass, and the LayerNorm pass with the e4m3 side output
+ab("fp8 row quantisation 163840 x 1024", lambda lib: lambda: lib.nova_quantize_rows_fp8(x.data_ptr(), x8.data_ptr(), xs.data_ptr(), S * L, D, st))
+ab("LayerNorm/residual pass + fp8 side output", lambda lib: lambda: lib.nova_row_norm_fp8(x.data_ptr(), out_.data_ptr(), gam.data_ptr(), bet.data_ptr(), res_.data_ptr(), x8.data_ptr(), xs.data_ptr(), S * L, D, 1e-5, st))
 
