@@ -679,6 +679,88 @@ int nova_pointset_posenc(const float* x, const float* scale, const float* div, c
 int nova_pointset_posenc_bwd(const float* x, const float* scale, const float* div, const float* g, float* gx, float* gs,
                              float* ws, int S, int N, int E, void* stream);
 
+/* Fused point embedding, forward and backward: the lift of the per-point inputs x [S, N, C] (float32) to the model width
+ * through W [E, C] (the layout of nn.Linear.weight) and the broadcast additions that follow it, out [S, N, E] (float32)
+ * written once. It is the step in front of every other point-set operation of the reference's two point-cloud forwards,
+ * diffnext/models/transformers/transformer_pointcloud_nova.py: point_embed = nn.Linear(point_cloud_dim, 768) followed by
+ * x = x + self.pos_embed[:, :x.shape[1], :] (:562-565, :712-716); the per-cloud rows broadcast over the points,
+ * x + expanded_cluster_features (:753-756), x + timestep_emb.unsqueeze(1) (:759-760), x + text_emb (:772), and the same two in
+ * AutoregressiveDiffusion.forward (:294, :297); EdgeAligner's spatial_embed = nn.Linear(3, embed_dim) (:174) added onto a
+ * per-point base, final_features = aligned_features + spatial_features (:218-221); PointCloudPatchEmbed / PointCloudPosEmbed at
+ * patch size 1 (:315-327, :340-346). In torch that is a K = C GEMM that writes [S, N, E] and one full read-and-write pass per
+ * addend, and in the backward one read of the incoming gradient per consumer. Neither pass stores anything of size N E here.
+ * bias [E], pos [N, E] (shared by all clouds), cond [S, E] (one row per cloud) and base [S, N, E] may each be NULL.
+ * nova_pointset_embed: for row i of cloud s and channel e, every operation rounded once to float32:
+ *     v = x[s, i, 0] * W[e, 0]
+ *     v = fmaf(x[s, i, k], W[e, k], v)          for k = 1 .. C-1 in that order
+ *     v = v + bias[e]                           each of the four additions only when its pointer is given, in this order
+ *     v = v + pos[i, e]
+ *     v = v + cond[s, e]
+ *     v = v + base[s, i, e]
+ *     out[s, i, e] = v
+ *   An addend that is not given is no addition (not an addition of 0: -0 stays -0). So out with base is bitwise the float32
+ *   sum of out-without-base and base, and likewise for cond, pos and bias, each onto the result without it and the later ones.
+ *   Non-finite inputs are not checked (a training path); NaN comes out as in torch.
+ * nova_pointset_embed_bwd: from g [S, N, E] = dLoss/dout and the forward's x and W, in one pass over g, whichever is wanted of
+ *     gx [S, N, C]   gx[s, i, c]  = sum_e g[s, i, e] W[e, c]
+ *     gWs [S, E, C]  gWs[s, e, c] = sum over the rows i of cloud s of g[s, i, e] x[s, i, c]     PER CLOUD
+ *     gcs [S, E]     gcs[s, e]    = sum over the rows i of cloud s of g[s, i, e]                PER CLOUD
+ *   gcs is the gradient of cond; summed over the clouds it is the gradient of bias, and gWs summed over the clouds the
+ *   gradient of W (nova_pointset_embed_sum_clouds). The gradient of base is g itself: no kernel runs for it. The gradient of
+ *   pos is nova_pointset_embed_pos_bwd.
+ *   Order of the sums (part of the definition: it fixes the bits; it depends on (N, C, E) alone, never on S, the launch split
+ *   or the cloud's position):
+ *     over e within a row (gx): the channels are cut into blocks of 256; lane l of one wave of 64 holds the channels
+ *       256 b + 4 l + j, j = 0 .. 3, of block b. Per block the lane adds to +0 its terms acc = fmaf(g[e], W[e, c], acc) in
+ *       ascending j, skipping channels past E - 1 (a lane with no channel keeps +0). The 64 lane sums are added by six
+ *       pairwise steps in which both partners take a + b: lanes i <-> 7 - i inside each group of 8, then xor 1, xor 2,
+ *       i <-> 15 - i inside each row of 16, rows 0|1 and 2|3 of 16 lanes, the two halves of 32 (the pairing of
+ *       nova_pointset_soft_cluster). The block sums are added to +0 in ascending block order.
+ *     over the rows of a chunk (gWs, gcs): the cloud is cut into chunks of NOVA_EMBED_CHUNK = 128 consecutive rows. Inside a
+ *       chunk starting at row b, wave w of 4 accumulates from +0 the rows b + w, b + w + 4, ... , b + w + 124 in that order,
+ *       skipping those past N - 1 (a wave with no row keeps +0), each step acc = fmaf(g[i, e], x[i, c], acc) for gWs and
+ *       acc = acc + g[i, e] for gcs; the four waves are added as ((w0 + w1) + w2) + w3.
+ *     over the chunks of a cloud: the chunk sums are added to +0 in ascending chunk order, through the workspace.
+ *   No atomics.
+ *   A NULL gx, gWs or gcs means "not wanted" and the work that only serves it is skipped; they may not all be NULL.
+ *   ws: a caller-provided workspace of S * ceil(N / NOVA_EMBED_CHUNK) * E * (C + 1) floats, read and written only when gWs or
+ *   gcs is given; its contents after the call are unspecified.
+ * nova_pointset_embed_sum_clouds: out[j] = the sum of per_cloud[s, j] added to +0 in ascending s = 0 .. S-1, one thread per
+ *   element j < n: the gradient of W (per_cloud = gWs, n = E C) and of bias (per_cloud = gcs, n = E), to be formed ONCE after
+ *   every launch has written its clouds, so it does not depend on the launch split. nova_pointset_soft_cluster_sum_clouds
+ *   has the same contract but ends at 3 * 32 elements. NOVA_ERR_SHAPE for n outside 1 .. NOVA_EMBED_MAX_DIM *
+ *   NOVA_EMBED_MAX_IN; S <= 0 returns 0 (out is not written); then NOVA_ERR_ARG for a null per_cloud or out and for out
+ *   overlapping per_cloud.
+ * nova_pointset_embed_pos_bwd: gpos[i, e] = (accumulate ? gpos[i, e] : +0) + g[0, i, e] + g[1, i, e] + ... + g[S-1, i, e], added
+ *   left to right, one thread per 16 bytes (per element where N E % 4 != 0 or a pointer is off 16 bytes: the same bits).
+ *   Called once per launch of clouds in ascending order, accumulate == 0 on the first call only, the result is one
+ *   left-to-right sum over all clouds whatever the split. It is a second read of g, made only when pos needs a gradient
+ *   (torch's g.sum(0) is the same read). NOVA_ERR_SHAPE for E, N, S > 65535 as below; S <= 0 returns 0; then NOVA_ERR_ARG for
+ *   a null g or gpos and for gpos overlapping g.
+ * Consequences: out, gx, gWs and gcs of a cloud depend on (x[s], W, bias, pos, cond[s], base[s] or g[s], N, C, E) alone:
+ * bitwise the same for every batch, launch split, position in the batch and run, and for every alignment of the pointers
+ * (rows that start on 16 bytes move 16 bytes per lane, on 8 bytes 8, otherwise 4; a lane keeps its channels). Where every
+ * product and sum is exact in float32 (small integers) all results are the exact ones.
+ * Limits: 1 <= C <= NOVA_EMBED_MAX_IN; 1 <= E <= NOVA_EMBED_MAX_DIM; 1 <= N <= NOVA_EMBED_MAX_POINTS; clouds in grid.y, at
+ * most 65535 per call; element offsets are 64-bit throughout (S N E passes 2^31).
+ * Errors of the forward and the backward, in this order, before any device work: NOVA_ERR_SHAPE for C outside its range, for
+ * E outside its range, for N outside its range, for S > 65535. S <= 0 returns 0 after these, before any pointer is looked at.
+ * Then NOVA_ERR_ARG for a null x, W or out (forward), a null x, W or g (backward); backward only: NOVA_ERR_ARG for gx, gWs and
+ * gcs all NULL, then for gWs or gcs given with a null ws; last, NOVA_ERR_ARG when an output (out; gx, gWs, gcs, ws) overlaps
+ * an input (x, W, bias, pos, cond, base; x, W, g) or another output.
+ * Added without a version bump (the number is pinned by the tests of three earlier entries; a library without the new
+ * symbols fails to bind, loudly). */
+#define NOVA_EMBED_MAX_IN 8
+#define NOVA_EMBED_MAX_DIM 4096
+#define NOVA_EMBED_MAX_POINTS 65536
+#define NOVA_EMBED_CHUNK 128
+int nova_pointset_embed(const float* x, const float* W, const float* bias, const float* pos, const float* cond,
+                        const float* base, float* out, int S, int N, int C, int E, void* stream);
+int nova_pointset_embed_bwd(const float* x, const float* W, const float* g, float* gx, float* gWs, float* gcs, float* ws,
+                            int S, int N, int C, int E, void* stream);
+int nova_pointset_embed_sum_clouds(const float* per_cloud, float* out, int S, int n, void* stream);
+int nova_pointset_embed_pos_bwd(const float* g, float* gpos, int S, int N, int E, int accumulate, void* stream);
+
 /* Nearest match with indices, and its backward: the primitive under the Chamfer-type training losses of the reference,
  * robust_chamfer_distance on distChamfer (train_newloss.py:316-349) and the edge-consistency term (train_newloss.py:449-457:
  * torch.cdist(subset1, subset2).min(dim=1), mean), which in PyTorch keep a [B, N, M] cdist matrix alive for the backward.
