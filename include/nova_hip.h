@@ -761,6 +761,73 @@ int nova_pointset_embed_bwd(const float* x, const float* W, const float* g, floa
 int nova_pointset_embed_sum_clouds(const float* per_cloud, float* out, int S, int n, void* stream);
 int nova_pointset_embed_pos_bwd(const float* g, float* gpos, int S, int N, int E, int accumulate, void* stream);
 
+/* Fused point head, forward and backward: the projection of the transformer's rows x [S, N, E] to the per-point outputs
+ * through W [C, E] (the layout of nn.Linear.weight) and bias [C] (may be NULL), out [S, N, C] (float32). It is the last layer
+ * of both point-cloud models of the reference, diffnext/models/transformers/transformer_pointcloud_nova.py:
+ * self.output_proj = nn.Linear(embed_dim, 3) (:444, :611) applied as x = self.output_proj(x); x.view(B, -1, 3) (:512-515,
+ * :778-781); train_newloss.py wraps it in GradientGuard(max_grad_norm=15.0) (:34-43, :681-684, :782), a torch.clamp of the
+ * incoming gradient to +-15 in training mode, and PointCloudLoss consumes the result (:469). In torch that is a GEMM of
+ * output width 3, three more degenerate GEMMs in the backward and one pass for the clamp; here the forward reads x once and
+ * the backward reads x at most once and writes gx at most once. It is nova_pointset_embed with the roles swapped.
+ * x is const void* with a nova_dtype code `dtype`: NOVA_F32, NOVA_BF16 or NOVA_F16. Every element is converted EXACTLY to
+ * float32 on load; everything after that is float32, every operation rounded once. W, bias, out, g, gWs, gbs, ws are float32.
+ * Lanes and blocks (part of the definition, the same for every dtype): the channels are cut into blocks of 512; lane l of one
+ * wave of 64 holds the channels 512 b + 8 l + j, j = 0 .. 7, of block b.
+ * nova_pointset_head: for row i of cloud s and output c:
+ *     lane l:  a_l = +0;  a_l = fmaf(x[s, i, e], W[c, e], a_l)  over the lane's channels e <= E - 1 in ascending e (block after
+ *              block, j ascending inside a block; a lane with no channel keeps +0)
+ *     t = the 64 lane sums added by six pairwise steps in which both partners take a + b: lanes i <-> 7 - i inside each group
+ *         of 8, then xor 1, xor 2, i <-> 15 - i inside each row of 16, rows 0|1 and 2|3 of 16 lanes, the two halves of 32 (the
+ *         pairing of nova_pointset_embed_bwd's gx)
+ *     out[s, i, c] = t + bias[c]                only when bias is given: an absent bias is no addition (not an addition of 0)
+ *   The order is the lane's channels ascending, then the wave tree, then the bias once; it depends on E alone: never on the
+ *   dtype, the alignment of x, the grid shape, the launch split or the cloud's position.
+ * nova_pointset_head_bwd: from g [S, N, C] = dLoss/dout (float32), x and W, whichever is wanted of
+ *     gx [S, N, E]   gx[s, i, e]  = sum_c g'[s, i, c] W[c, e]           in x's dtype
+ *     gWs [S, C, E]  gWs[s, c, e] = sum over the rows i of cloud s of g'[s, i, c] x[s, i, e]     PER CLOUD, float32
+ *     gbs [S, C]     gbs[s, c]    = sum over the rows i of cloud s of g'[s, i, c]                PER CLOUD, float32
+ *   g' = g when clamp <= 0 (or NaN); with clamp > 0 every g is replaced on load by g < -clamp ? -clamp : g > clamp ? clamp : g,
+ *   which is torch.clamp(g, -clamp, clamp): exact, no rounding, a NaN stays a NaN (the reference's GradientGuard).
+ *   gWs and gbs summed over the clouds are the gradients of W and bias: nova_pointset_embed_sum_clouds with n = C E and n = C,
+ *   called once after every launch has written its clouds (its contract, n up to NOVA_EMBED_MAX_DIM * NOVA_EMBED_MAX_IN, fits).
+ *   gx: v = g'[c = 0] * W[0, e], then v = fmaf(g'[c], W[c, e], v) for c = 1 .. C-1 in that order (one multiplication and C - 1
+ *     fused multiply-adds in float32), stored in x's dtype with ONE round-to-nearest-even (float32: as it is); f16 beyond
+ *     65504 becomes an infinity, as torch's cast does.
+ *   Order of the row sums (part of the definition; it depends on N alone, never on S, the launch split or the cloud's
+ *   position): the cloud is cut into chunks of NOVA_HEAD_CHUNK = 128 consecutive rows. Inside a chunk starting at row b,
+ *     wave w of 4 accumulates from +0 the rows b + w, b + w + 4, ... , b + w + 124 in that order, skipping those past N - 1 (a
+ *     wave with no row keeps +0), each step acc = fmaf(g'[i, c], x[i, e], acc) for gWs and acc = acc + g'[i, c] for gbs; the
+ *     four waves are added as ((w0 + w1) + w2) + w3. The chunk sums are added to +0 in ascending chunk order, through the
+ *     workspace.
+ *   No atomics.
+ *   A NULL gx, gWs or gbs means "not wanted" and the work that only serves it is skipped (x is read only when gWs is given
+ *   and may be NULL otherwise); they may not all be NULL.
+ *   ws: a caller-provided workspace of S * ceil(N / NOVA_HEAD_CHUNK) * C * (E + 1) floats (per cloud and chunk the [C, E]
+ *   partial of gWs, then the [C] partial of gbs), read and written only when gWs or gbs is given; its contents after the call
+ *   are unspecified.
+ * Consequences: out, gx, gWs and gbs of a cloud depend on (x[s], W, bias, g[s], clamp, N, C, E) alone: bitwise the same for
+ * every batch, launch split, position in the batch and run, and for every alignment of the pointers (rows that start on 16
+ * bytes move 16 bytes per access, else 8, 4 or, for the 16-bit types, 2; a lane keeps its channels). out of a bf16 or f16 x
+ * is bitwise out of that x cast to float32, and its gx is bitwise that float32 gx rounded once. Where every product and sum
+ * is exact in float32 (small integers) all results are the exact ones. Non-finite inputs are not checked (a training path).
+ * Limits: 1 <= C <= NOVA_HEAD_MAX_OUT; 1 <= E <= NOVA_HEAD_MAX_DIM; 1 <= N <= NOVA_HEAD_MAX_POINTS; clouds in grid.y, at
+ * most 65535 per call; element offsets are 64-bit throughout.
+ * Errors of both, in this order, before any device work: NOVA_ERR_ARG for a null x, W or out (forward), a null x (when gWs is
+ * given), W or g (backward); NOVA_ERR_ARG for an unknown dtype code; NOVA_ERR_SHAPE for C outside its range, for E outside its
+ * range, for N outside its range, for S > 65535. S <= 0 returns 0 after these and writes nothing. Backward only: then
+ * NOVA_ERR_ARG for gx, gWs and gbs all NULL, then for gWs or gbs given with a null ws. Last, NOVA_ERR_ARG when an output (out;
+ * gx, gWs, gbs, ws) overlaps an input (x, W, bias; x, W, g) or another output.
+ * Added without a version bump (the number is pinned by the tests of earlier entries; a library without the new symbols
+ * fails to bind, loudly). */
+#define NOVA_HEAD_MAX_OUT 8
+#define NOVA_HEAD_MAX_DIM 4096
+#define NOVA_HEAD_MAX_POINTS 65536
+#define NOVA_HEAD_CHUNK 128
+int nova_pointset_head(const void* x, int dtype, const float* W, const float* bias, float* out, int S, int N, int C, int E,
+                       void* stream);
+int nova_pointset_head_bwd(const void* x, int dtype, const float* W, const float* g, float clamp, void* gx, float* gWs,
+                           float* gbs, float* ws, int S, int N, int C, int E, void* stream);
+
 /* Nearest match with indices, and its backward: the primitive under the Chamfer-type training losses of the reference,
  * robust_chamfer_distance on distChamfer (train_newloss.py:316-349) and the edge-consistency term (train_newloss.py:449-457:
  * torch.cdist(subset1, subset2).min(dim=1), mean), which in PyTorch keep a [B, N, M] cdist matrix alive for the backward.

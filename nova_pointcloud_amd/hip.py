@@ -112,6 +112,8 @@ SIGNATURES = {
     "nova_pointset_embed_bwd": [c_void_p] * 7 + [c_int] * 4 + [c_void_p],
     "nova_pointset_embed_sum_clouds": [c_void_p] * 2 + [c_int] * 2 + [c_void_p],
     "nova_pointset_embed_pos_bwd": [c_void_p] * 2 + [c_int] * 4 + [c_void_p],
+    "nova_pointset_head": [c_void_p, c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p],
+    "nova_pointset_head_bwd": [c_void_p, c_int, c_void_p, c_void_p, c_float] + [c_void_p] * 4 + [c_int] * 4 + [c_void_p],
     "nova_pointset_assignment": [c_void_p] * 5 + [c_int, c_int, c_float, c_float] + [c_int] * 3 + [c_void_p, c_void_p],
     "nova_pointset_assignment_rounds": [c_void_p, c_void_p, c_int, c_int, c_void_p],
     "nova_modulate_rows": [c_void_p] * 3 + [c_long, c_int, c_int, c_void_p],
