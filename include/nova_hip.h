@@ -828,6 +828,85 @@ int nova_pointset_head(const void* x, int dtype, const float* W, const float* bi
 int nova_pointset_head_bwd(const void* x, int dtype, const float* W, const float* g, float clamp, void* gx, float* gWs,
                            float* gbs, float* ws, int S, int N, int C, int E, void* stream);
 
+/* Fused bias-dropout-residual, forward and backward: the elementwise chains of the transformer body of the reference's
+ * point-cloud models, diffnext/models/transformers/transformer_pointcloud_nova.py: nn.TransformerEncoderLayer(d_model, nhead,
+ * dim_feedforward=4*d_model, dropout=0.1, batch_first=True, norm_first=True) with the default ReLU, stacked 8 or `depth`
+ * times (:433-441, :590-598) and run at :510 and :775; dropout=0.1 is what train_newloss.py trains with (:652, :673). A
+ * training step runs each layer as
+ *     x = x + dropout1(out_proj(attn(norm1(x))))                      bias + dropout + residual on [B, N, E], twice per layer
+ *     x = x + dropout2(linear2(dropout(relu(linear1(norm2(x))))))     bias + ReLU + dropout on [B, N, 4E], once per layer
+ * In torch each chain reads and writes the activation three or four times and keeps a [rows, D] boolean mask drawn from the
+ * device generator. Here every operand is read once and the output written once, and the mask is a pure function of
+ * (seed, subsequence, element index): it is regenerated in the backward, never stored, and a CPU program can restate it.
+ * x, residual, out, g, gx are [rows, D] in one nova_dtype (NOVA_F32, NOVA_BF16, NOVA_F16), rows contiguous; bias and
+ * gbias_parts are float32.
+ * The mask (part of the definition). The generator is Philox4x32-10: ten rounds of
+ *     p0 = 0xD2511F53 * c0,  p1 = 0xCD9E8D57 * c2                      (32 x 32 -> 64 bits)
+ *     (c0, c1, c2, c3) = (hi(p1) ^ c1 ^ k0,  lo(p1),  hi(p0) ^ c3 ^ k1,  lo(p0))
+ *     (k0, k1) = (k0 + 0x9E3779B9, k1 + 0xBB67AE85)                    (mod 2^32; the key is bumped after every round)
+ *   For the element with flat index i = (first_row + row) * D + col (64-bit, counted from the start of the LOGICAL tensor:
+ *   first_row is the row index of x[0] in it, so a slice sees the mask of its place) the counter is
+ *   (lo32(i >> 2), hi32(i >> 2), lo32(subsequence), hi32(subsequence)), the key (lo32(seed), hi32(seed)), and the draw w(i) is
+ *   word i & 3 of the four output words (c0 .. c3 after the tenth round). The element is KEPT iff (uint64) w(i) >= T, where the
+ *   caller passes T = floor(p * 2^32) in 0 .. 2^32 as a 64-bit value: p = 0 (T = 0) keeps everything, p = 1 (T = 2^32) keeps
+ *   nothing, with no special case in the definition. When T == 0 no Philox is evaluated. scale is the caller's float32
+ *   nearest to 1 / (1 - p) (1 for p = 0; unused for p = 1, pass 0).
+ *   Known answers (counter; key; output), the first and third from Random123:
+ *     00000000 x 4; 00000000 x 2;                                   6627e8d5 e169c58d bc57ac4c 9b00dbd8
+ *     ffffffff x 4; ffffffff x 2;                                   408f276d 41c83b0e a20bc7c6 6d5451fd
+ *     243f6a88 85a308d3 13198a2e 03707344; a4093822 299f31d0;       d16cfe09 94fdcceb 5001e420 24126ea1
+ * nova_bias_dropout_add: per element, everything float32, every operation rounded once, nothing fused:
+ *     t = float32(x[i])                                      exact
+ *     t = t + bias[col]                                      only when bias is given: an absent bias is no addition
+ *     act == NOVA_DROPOUT_ACT_RELU:  t = t > 0 ? t : (t != t ? t : +0)       (a NaN stays a NaN, -0 and negatives become +0)
+ *     d = keep(i) ? t * scale : +0
+ *     o = residual given ? float32(residual[i]) + d : d
+ *     out[i] = o stored in the tensor's dtype with ONE round-to-nearest-even (float32: as it is)
+ *   A dropped element is +0 whatever t is. Torch's x * mask * scale makes a dropped infinity or NaN a NaN; this kernel does
+ *   not: only kept non-finite values propagate. No sums: there is no order to state in the forward.
+ *   NOVA_DROPOUT_ACT_RELU together with a residual is an error: the reference has no such site, and the backward relies on it.
+ * nova_bias_dropout_add_bwd: from g = dLoss/dout, whichever is wanted of gx (the tensor's dtype) and gbias_parts:
+ *     act == NOVA_DROPOUT_ACT_NONE:  v = keep(i) ? float32(g[i]) * scale : +0     the mask is regenerated; `out` is not read and
+ *                                                                              may be NULL; nothing of size rows x D was saved
+ *     act == NOVA_DROPOUT_ACT_RELU:  v = float32(out[i]) > 0 ? float32(g[i]) * scale : +0     reads the forward's saved output
+ *                                    and evaluates no Philox (torch's convention: threshold_backward gates on the result; a
+ *                                    dropped element has out = +0, and so has a kept one that the ReLU zeroed)
+ *     gx[i] = v stored with ONE round-to-nearest-even. A NULL gx means "not wanted".
+ *   gbias_parts: float32 [ceil(rows / NOVA_DROPOUT_CHUNK), D], or NULL for "not wanted". Row c, column col is the sum, started
+ *   from +0, of the float32 values v (BEFORE the store rounding) of the rows 128 c .. min(128 c + 127, rows - 1) at that
+ *   column, added in ascending row order: acc = acc + v, one float32 addition per row. One thread owns a column group and walks
+ *   the rows: no cross-lane reduction, no atomics. The gradient of the bias is the sum of the chunk rows added to +0 in
+ *   ascending chunk order: nova_pointset_embed_sum_clouds(gbias_parts, gbias, chunks, D, stream), whose contract fits
+ *   (n = D up to 32768, any number of rows). So that the chunks of a slice are the chunks of the logical tensor, first_row
+ *   must be a multiple of NOVA_DROPOUT_CHUNK = 128 when gbias_parts is given.
+ * Consequences: out, gx and gbias_parts depend on (the operands, T, scale, seed, subsequence, first_row, D) alone: bitwise the
+ * same for every run, every split of the rows into calls at multiples of 128 and every alignment of the pointers. Kernel
+ * shape (no part of the definition): 16 bytes per lane and access, 4 float32 or 8 16-bit elements, where D is a multiple of
+ * that count and every pointer is on 16 bytes, one Philox evaluation serving 4 consecutive elements; otherwise element by
+ * element, the same bits. Element offsets are 64-bit throughout. Non-finite inputs are not checked (a training path).
+ * Limits: 1 <= D <= NOVA_DROPOUT_MAX_DIM; rows <= NOVA_DROPOUT_MAX_ROWS per call; first_row + rows <= 2^48.
+ * Errors of both, in this order, before any device work: (1) NOVA_ERR_ARG for a null x or out (forward), a null g (backward);
+ * (2) NOVA_ERR_ARG for an unknown dtype code; (3) NOVA_ERR_ARG for an unknown act code, then (forward) for
+ * NOVA_DROPOUT_ACT_RELU with a residual; (4) backward: NOVA_ERR_ARG for NOVA_DROPOUT_ACT_RELU with a null out;
+ * (5) NOVA_ERR_SHAPE for D outside its range, then for rows above NOVA_DROPOUT_MAX_ROWS; (6) NOVA_ERR_ARG for T > 2^32;
+ * (7) NOVA_ERR_ARG for first_row < 0, then for first_row + rows > 2^48; (8) backward: NOVA_ERR_ARG for first_row not a
+ * multiple of 128 when gbias_parts is given; (9) backward: NOVA_ERR_ARG for gx and gbias_parts both NULL. rows <= 0 returns 0
+ * after these and writes nothing. Last, (10) NOVA_ERR_ARG when an output (out; gx, gbias_parts) overlaps an input (x, bias,
+ * residual; g, and out with NOVA_DROPOUT_ACT_RELU) or another output.
+ * Added without a version bump (the number is pinned by the tests of earlier entries; a library without the new symbols
+ * fails to bind, loudly). */
+#define NOVA_DROPOUT_MAX_DIM 16384
+#define NOVA_DROPOUT_MAX_ROWS 1073741824
+#define NOVA_DROPOUT_CHUNK 128
+#define NOVA_DROPOUT_ACT_NONE 0
+#define NOVA_DROPOUT_ACT_RELU 1
+int nova_bias_dropout_add(const void* x, int dtype, const float* bias, const void* residual, void* out, long long rows, int D,
+                          long long first_row, unsigned long long T, float scale, unsigned long long seed,
+                          unsigned long long subsequence, int act, void* stream);
+int nova_bias_dropout_add_bwd(const void* g, const void* out, int dtype, void* gx, float* gbias_parts, long long rows, int D,
+                              long long first_row, unsigned long long T, float scale, unsigned long long seed,
+                              unsigned long long subsequence, int act, void* stream);
+
 /* Nearest match with indices, and its backward: the primitive under the Chamfer-type training losses of the reference,
  * robust_chamfer_distance on distChamfer (train_newloss.py:316-349) and the edge-consistency term (train_newloss.py:449-457:
  * torch.cdist(subset1, subset2).min(dim=1), mean), which in PyTorch keep a [B, N, M] cdist matrix alive for the backward.

@@ -114,6 +114,10 @@ SIGNATURES = {
     "nova_pointset_embed_pos_bwd": [c_void_p] * 2 + [c_int] * 4 + [c_void_p],
     "nova_pointset_head": [c_void_p, c_int] + [c_void_p] * 3 + [c_int] * 4 + [c_void_p],
     "nova_pointset_head_bwd": [c_void_p, c_int, c_void_p, c_void_p, c_float] + [c_void_p] * 4 + [c_int] * 4 + [c_void_p],
+    "nova_bias_dropout_add": [c_void_p, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, ctypes.c_longlong, ctypes.c_ulonglong, c_float,
+                              ctypes.c_ulonglong, ctypes.c_ulonglong, c_int, c_void_p],
+    "nova_bias_dropout_add_bwd": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_longlong, c_int, ctypes.c_longlong, ctypes.c_ulonglong, c_float,
+                                  ctypes.c_ulonglong, ctypes.c_ulonglong, c_int, c_void_p],
     "nova_pointset_assignment": [c_void_p] * 5 + [c_int, c_int, c_float, c_float] + [c_int] * 3 + [c_void_p, c_void_p],
     "nova_pointset_assignment_rounds": [c_void_p, c_void_p, c_int, c_int, c_void_p],
     "nova_modulate_rows": [c_void_p] * 3 + [c_long, c_int, c_int, c_void_p],

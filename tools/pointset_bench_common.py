@@ -1,5 +1,5 @@
 """Seeded inputs and device-event timers shared by the point-set bench tools (chamfer_matrix_bench, emd_matrix_bench,
-fps_bench, assignment_bench, knn_bench, interp_bench, chamfer_loss_bench, interp_grad_bench, emd_loss_bench, neighbor_bench, soft_cluster_bench, posenc_bench, point_embed_bench, point_head_bench). torch is imported on first use: knn_bench's and interp_bench's parent
+fps_bench, assignment_bench, knn_bench, interp_bench, chamfer_loss_bench, interp_grad_bench, emd_loss_bench, neighbor_bench, soft_cluster_bench, posenc_bench, point_embed_bench, point_head_bench, dropout_add_bench). torch is imported on first use: knn_bench's and interp_bench's parent
 processes do no GPU work."""
 
 
