@@ -151,6 +151,29 @@ int nova_attn_bwd(const void* q_scaled, const void* k, const void* v, const void
                   long qkv_row_stride, long o_row_stride, long do_row_stride, long dqkv_row_stride, float scale,
                   const int* key_limit, void* stream);
 
+/* The same two calls for cross-attention, Lq queries against Lk keys (bf16, head_dim 64 or 96): the reference's
+ * nn.MultiheadAttention(embed_dim, num_heads, batch_first=True) of EdgeAligner (transformer_pointcloud_nova.py:164), called with
+ * query = the current subset's edge features and key = value = the concatenated edge features of the subsets generated so far
+ * (:211-215), and the one of AutoregressiveDiffusion (:236) over all generated subsets (:265-269). The same kernels, with the
+ * lengths and the row strides of the two sides passed apart: q, o, dO and dq are [S, Lq, heads * head_dim] rows with strides
+ * q_row_stride, o_row_stride, do_row_stride and dq_row_stride; k, v are [S, Lk, ...] rows with kv_row_stride, dk and dv with
+ * dkv_row_stride (strides in elements, 16-byte multiples; Lq * q_row_stride, Lq * o_row_stride, Lq * do_row_stride and
+ * Lk * kv_row_stride each below 2 GiB in bytes). q_scaled, lse, the formulas and the factor conventions are those above with
+ * the sum over j running to Lk: lse and delta_scratch are [S, heads, Lq] f32; dq is the gradient of the UNSCALED q [Lq rows],
+ * dk and dv have Lk rows. key_limit (NULL = no mask): int32 [Lq], non-decreasing, each in [1, Lk] - query l attends to keys
+ * [0, key_limit[l]). dk / dv rows of keys that no query sees are written as 0; nothing is written past row Lq / Lk or outside
+ * a head's columns. With Lq == Lk and equal strides on both sides the two calls return the bits of nova_attn_fwd_lse /
+ * nova_attn_bwd (tests/test_gpu_attn_cross.py). Refused before any launch: null pointers (NOVA_ERR_ARG); head_dim other than 64
+ * or 96, strides that are not 16-byte multiples, Lk <= 0 with Lq > 0, a span of 2 GiB or more, a grid above 2^31 - 1 workgroups
+ * (NOVA_ERR_SHAPE). S == 0 or Lq == 0 launches nothing and returns 0. */
+int nova_attn_cross_fwd_lse(const void* q_scaled, const void* k, const void* v, void* o, float* lse, int S, int heads, int Lq, int Lk,
+                            int head_dim, long q_row_stride, long kv_row_stride, long o_row_stride, const int* key_limit,
+                            void* stream);
+int nova_attn_cross_bwd(const void* q_scaled, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
+                        float* delta_scratch, void* dq, void* dk, void* dv, int S, int heads, int Lq, int Lk, int head_dim,
+                        long q_row_stride, long kv_row_stride, long o_row_stride, long do_row_stride, long dq_row_stride,
+                        long dkv_row_stride, float scale, const int* key_limit, void* stream);
+
 /* ---- training side, pointwise -------------------------------------------
  * The activation between the two projections of an MLP, forward and backward, n contiguous elements of `dtype`
  * (n a multiple of 16 bytes' worth: 4 floats / 8 16-bit values), arithmetic in f32:

@@ -3,7 +3,9 @@
 `attention(q, k, v, attn_mask)` is F.scaled_dot_product_attention (no dropout; no mask, or the block-causal frame mask of multi-frame
 training passed as a per-query key limit) for bf16 device tensors with head_dim 64 / 96:
 forward on `attn_bf16` with the row log-sum-exp kept, backward on `attn_bwd_dq` / `attn_bwd_dkv` (csrc/attn_bwd.hip;
-reference vision_transformer.py:63 under the training forward transformer_3d.py:79-100).
+reference vision_transformer.py:63 under the training forward transformer_3d.py:79-100). k and v may have another length
+than q (cross-attention: EdgeAligner's nn.MultiheadAttention call, transformer_pointcloud_nova.py:211-215): the same kernels
+through `nova_attn_cross_fwd_lse` / `nova_attn_cross_bwd`.
 
 `fused_norm(x, ...)` is the LayerNorm family of the blocks as ONE row kernel forward and ONE backward (csrc/rowops.hip,
 csrc/rownorm_bwd.hip): y = LN(x) [* gamma + beta] [* (1 + scale) + shift] [* gate] [+ res] - the post-norm residual of a ViT
@@ -27,22 +29,23 @@ _KEY_LIMITS = {}  # id(mask tensor) -> (version, key_limit or None): the O(L^2) 
 
 
 def key_limit_of_mask(attn_mask):
-    """int32 [L] `key_limit` with mask[i, j] visible <=> j < key_limit[i] when the [L, L] mask (additive 0 / -inf as the reference builds
-    it, embeddings.py:247-260, or boolean) has that form with non-decreasing limits >= 1 - the block-causal frame mask - else None."""
-    if attn_mask is None or attn_mask.dim() != 2 or attn_mask.shape[0] != attn_mask.shape[1] or not attn_mask.is_cuda:
+    """int32 [Lq] `key_limit` with mask[i, j] visible <=> j < key_limit[i] when the [Lq, Lk] mask (additive 0 / -inf as the reference
+    builds it, embeddings.py:247-260, or boolean) has that form with non-decreasing limits in [1, Lk] - the block-causal frame mask,
+    square or, for cross-attention, rectangular - else None."""
+    if attn_mask is None or attn_mask.dim() != 2 or attn_mask.shape[0] < 1 or attn_mask.shape[1] < 1 or not attn_mask.is_cuda:
         return None
     hit = _KEY_LIMITS.get(id(attn_mask))
     if hit is not None and hit[0] == attn_mask._version and hit[2]() is attn_mask:
         return hit[1]
     import weakref
 
-    L = attn_mask.shape[0]
+    Lk = attn_mask.shape[1]
     allowed = attn_mask if attn_mask.dtype == torch.bool else attn_mask > float("-inf")
     if attn_mask.dtype != torch.bool and not bool(((attn_mask == 0) | ~allowed).all()):
         limit = None  # finite non-zero biases: not a pure visibility mask
     else:
         limit = allowed.sum(-1).to(torch.int32)
-        prefix = torch.arange(L, device=attn_mask.device)[None, :] < limit[:, None]
+        prefix = torch.arange(Lk, device=attn_mask.device)[None, :] < limit[:, None]
         ok = bool(torch.equal(prefix, allowed)) and bool((limit >= 1).all()) and bool((limit[1:] >= limit[:-1]).all())
         limit = limit.contiguous() if ok else None
     if len(_KEY_LIMITS) > 64:
@@ -51,19 +54,32 @@ def key_limit_of_mask(attn_mask):
     return limit
 
 
-def attention_supported(q, attn_mask=None):
-    """bf16 device tensors [S, heads, L, 64 | 96]; no mask, or a mask of the per-query key-limit form (key_limit_of_mask)."""
+def attention_supported(q, attn_mask=None, k=None):
+    """bf16 device tensors [S, heads, L, 64 | 96]; no mask, or a mask of the per-query key-limit form (key_limit_of_mask). `k`: the key
+    tensor of a cross-attention call [S, heads, Lk, head_dim] (None: self-attention, keys shaped as q); a mask must then be [Lq, Lk]."""
     if not (_ENABLED and q.is_cuda and q.dtype == torch.bfloat16 and q.shape[-1] in (64, 96) and q.dim() == 4):
         return False
-    return attn_mask is None or (attn_mask.shape[-1] == q.shape[-2] and key_limit_of_mask(attn_mask) is not None)
+    Lk = q.shape[-2]
+    if k is not None:
+        if not (k.is_cuda and k.dtype == torch.bfloat16 and k.dim() == 4 and tuple(k.shape[:2]) == tuple(q.shape[:2])
+                and k.shape[-1] == q.shape[-1] and k.shape[-2] >= 1):
+            return False
+        Lk = k.shape[-2]
+    return attn_mask is None or (attn_mask.dim() == 2 and tuple(attn_mask.shape) == (q.shape[-2], Lk) and key_limit_of_mask(attn_mask) is not None)
 
 
 class NovaAttentionFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, key_limit=None):
         S, h, L, d = q.shape
-        if k.shape != q.shape or v.shape != q.shape:
-            raise ValueError("nova attention (training) is self-attention: q, k, v must share one shape [S, heads, L, head_dim]")
+        if k.dim() != 4 or v.shape != k.shape or tuple(k.shape[:2]) != (S, h) or k.shape[-1] != d:
+            raise ValueError("nova attention (training): q [S, heads, Lq, head_dim], k and v of one shape [S, heads, Lk, head_dim], got "
+                             f"{tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+        Lk = k.shape[2]
+        if Lk < 1 and L > 0:
+            raise ValueError("nova attention (training): no keys")
+        if key_limit is not None and tuple(key_limit.shape) != (L,):
+            raise ValueError(f"nova attention (training): the key limit has one entry per query, [{L}], got {tuple(key_limit.shape)}")
         hip.load()
         stats["attention_calls"] += 1
         scale = 1.0 / math.sqrt(d)
@@ -72,8 +88,12 @@ class NovaAttentionFunction(torch.autograd.Function):
         kt, vt = k.transpose(1, 2).contiguous(), v.transpose(1, 2).contiguous()
         o = torch.empty(S, L, h, d, dtype=torch.bfloat16, device=q.device)
         lse = torch.empty(S, h, L, dtype=torch.float32, device=q.device)
-        hip.call("nova_attn_fwd_lse", qt.data_ptr(), kt.data_ptr(), vt.data_ptr(), o.data_ptr(), lse.data_ptr(), S, h, L, d, h * d, h * d,
-                 hip.ptr(key_limit), hip.stream_ptr())
+        if Lk == L:  # self-attention lengths: the entry points and the bits this path has always had
+            hip.call("nova_attn_fwd_lse", qt.data_ptr(), kt.data_ptr(), vt.data_ptr(), o.data_ptr(), lse.data_ptr(), S, h, L, d, h * d, h * d,
+                     hip.ptr(key_limit), hip.stream_ptr())
+        else:
+            hip.call("nova_attn_cross_fwd_lse", qt.data_ptr(), kt.data_ptr(), vt.data_ptr(), o.data_ptr(), lse.data_ptr(), S, h, L, Lk, d,
+                     h * d, h * d, h * d, hip.ptr(key_limit), hip.stream_ptr())
         ctx.save_for_backward(qt, kt, vt, o, lse, key_limit)
         ctx.scale = scale
         return o.transpose(1, 2)
@@ -85,20 +105,29 @@ class NovaAttentionFunction(torch.autograd.Function):
         do = d_out.transpose(1, 2).to(torch.bfloat16).contiguous()
         delta = torch.empty(S, h, L, dtype=torch.float32, device=do.device)  # filled by the library: sum_c dO * O
         dq, dk, dv = torch.empty_like(qt), torch.empty_like(kt), torch.empty_like(vt)
-        hip.call("nova_attn_bwd", qt.data_ptr(), kt.data_ptr(), vt.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(),
-                 delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), S, h, L, d, h * d, h * d, h * d, h * d, ctx.scale,
-                 hip.ptr(key_limit), hip.stream_ptr())
+        Lk = kt.shape[1]
+        if Lk == L:
+            hip.call("nova_attn_bwd", qt.data_ptr(), kt.data_ptr(), vt.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(),
+                     delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), S, h, L, d, h * d, h * d, h * d, h * d, ctx.scale,
+                     hip.ptr(key_limit), hip.stream_ptr())
+        else:
+            hip.call("nova_attn_cross_bwd", qt.data_ptr(), kt.data_ptr(), vt.data_ptr(), o.data_ptr(), do.data_ptr(), lse.data_ptr(),
+                     delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), S, h, L, Lk, d, h * d, h * d, h * d, h * d, h * d, h * d,
+                     ctx.scale, hip.ptr(key_limit), hip.stream_ptr())
         return dq.transpose(1, 2), dk.transpose(1, 2), dv.transpose(1, 2), None
 
 
 def attention(q, k, v, attn_mask=None):
-    """softmax(q k^T / sqrt(d) [+ mask]) v for [S, heads, L, 64 | 96] bf16 device tensors, differentiable. `attn_mask`: None or an
-    [L, L] visibility mask of the per-query key-limit form (the block-causal frame mask of multi-frame training)."""
+    """softmax(q k^T / sqrt(d) [+ mask]) v for bf16 device tensors q [S, heads, Lq, 64 | 96], k and v [S, heads, Lk, same], differentiable;
+    Lk may differ from Lq (cross-attention). `attn_mask`: None or an [Lq, Lk] visibility mask of the per-query key-limit form (the
+    block-causal frame mask of multi-frame training)."""
     limit = None
     if attn_mask is not None:
         limit = key_limit_of_mask(attn_mask)
         if limit is None:
             raise ValueError("nova attention: the mask is not of the per-query key-limit form (check attention_supported first)")
+        if tuple(attn_mask.shape) != (q.shape[-2], k.shape[-2]):
+            raise ValueError(f"nova attention: the mask must be [Lq, Lk] = [{q.shape[-2]}, {k.shape[-2]}], got {tuple(attn_mask.shape)}")
     return NovaAttentionFunction.apply(q, k, v, limit)
 
 

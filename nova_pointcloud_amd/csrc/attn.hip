@@ -329,7 +329,7 @@ int attn_fwd(const void* q, const void* k, const void* v, void* o, int S, int he
   if (S <= 0 || Lq <= 0) return 0;
   if (hd != 64 && hd != 96) return set_error(NOVA_ERR_SHAPE, "attn_fwd: head_dim %d not built (have 64 and 96)", hd);
   if (Lk <= 0 || heads <= 0) return set_error(NOVA_ERR_SHAPE, "attn_fwd: bad Lk/heads");
-  if (klim && (!lse || !dtype_is16(dtype) || Lq != Lk)) return set_error(NOVA_ERR_ARG, "attn_fwd: a key-limit mask comes with the 16-bit training forward (Lq == Lk, log-sum-exp output)");
+  if (klim && (!lse || !dtype_is16(dtype))) return set_error(NOVA_ERR_ARG, "attn_fwd: a key-limit mask comes with the 16-bit training forward (log-sum-exp output)");
   if (lse && !dtype_is16(dtype)) return set_error(NOVA_ERR_ARG, "attn_fwd: the log-sum-exp output is built for the 16-bit kernels");
   const int align = dtype_is16(dtype) ? 8 : 4;  // 16-byte row alignment for the vector loads
   if (q_rs % align || kv_rs % align || o_rs % align) return set_error(NOVA_ERR_SHAPE, "attn_fwd: row strides must be 16-byte multiples");

@@ -16,6 +16,10 @@
 //                 reads of the same LDS image the row fragments come from.
 // S and dP are computed in both kernels (7 MFMA products instead of the minimal 5): the price of having no cross-workgroup
 // sum and of running every product in the orientation whose accumulator is directly the next product's operand.
+// Cross-attention (Lq queries, Lk keys; EdgeAligner's nn.MultiheadAttention call, transformer_pointcloud_nova.py:211-215) is the
+// same two kernels: each takes both lengths and a row stride per side, clamps its resident rows and its stores against its own
+// side and its streamed tiles against the other. Self-attention is Lq == Lk with equal strides - the same index values, so the
+// same bits - and the two launches have a grid each (ceil(Lq / 128) and ceil(Lk / 128) workgroups per sequence and head).
 #include "common.h"
 #include "nova_internal.h"
 
@@ -110,8 +114,8 @@ template <int HD>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                       const bf16_t* __restrict__ v, const bf16_t* __restrict__ d_o,
                                                       const float* __restrict__ lse, const float* __restrict__ delta,
-                                                      bf16_t* __restrict__ dq, int L, long qkv_rs, long do_rs, long dq_rs,
-                                                      float scale, int heads, int nq, const int* __restrict__ klim) {
+                                                      bf16_t* __restrict__ dq, int Lq, int Lk, long q_rs, long kv_rs, long do_rs,
+                                                      long dq_rs, float scale, int heads, int nq, const int* __restrict__ klim) {
   constexpr int NKS = HD / 16, NDB = HD / 32, TILE = tile_bytes<HD>();
   constexpr int BUF = 2 * TILE;  // [K | V]
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
@@ -122,33 +126,33 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq(const bf16_t* __restrict__
   const int sh = t / nq, qt = t - sh * nq;
   const int head = sh % heads, s = sh / heads;
   const int q0 = qt * 128 + wid * 32;
-  const int qrow = min(q0 + r, L - 1);
+  const int qrow = min(q0 + r, Lq - 1);
 
   // resident: Q~ and dO fragments of the lane's query (B operands), its lse and delta
   bf8v qf[NKS], dof[NKS];
   {
-    const bf16_t* qp = q + ((size_t)s * L + qrow) * qkv_rs + head * HD + 8 * hh;
-    const bf16_t* dp = d_o + ((size_t)s * L + qrow) * do_rs + head * HD + 8 * hh;
+    const bf16_t* qp = q + ((size_t)s * Lq + qrow) * q_rs + head * HD + 8 * hh;
+    const bf16_t* dp = d_o + ((size_t)s * Lq + qrow) * do_rs + head * HD + 8 * hh;
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
       qf[ks] = *reinterpret_cast<const bf8v*>(qp + 16 * ks);
       dof[ks] = *reinterpret_cast<const bf8v*>(dp + 16 * ks);
     }
   }
-  const float lse_q = lse[((size_t)s * heads + head) * L + qrow];
-  const float del_q = delta[((size_t)s * heads + head) * L + qrow];
+  const float lse_q = lse[((size_t)s * heads + head) * Lq + qrow];
+  const float del_q = delta[((size_t)s * heads + head) * Lq + qrow];
   // key limit of the lane's query (block-causal frame mask of multi-frame training: keys [0, klim[q]) are visible, klim
-  // non-decreasing - attn16.hip MASK); without a mask every key below L
-  const int kl_q = klim ? min(klim[qrow], L) : L;
-  const int k_end = klim ? min(klim[min(qt * 128 + 127, L - 1)], L) : L;  // the workgroup's last row sees the most keys
+  // non-decreasing - attn16.hip MASK); without a mask every key below Lk
+  const int kl_q = klim ? min(klim[qrow], Lk) : Lk;
+  const int k_end = klim ? min(klim[min(qt * 128 + 127, Lq - 1)], Lk) : Lk;  // the workgroup's last row sees the most keys
 
-  const char* kb_ = reinterpret_cast<const char*>(k + (size_t)s * L * qkv_rs + head * HD);
-  const char* vb_ = reinterpret_cast<const char*>(v + (size_t)s * L * qkv_rs + head * HD);
-  const uint32_t rowB = (uint32_t)qkv_rs * 2u;
+  const char* kb_ = reinterpret_cast<const char*>(k + (size_t)s * Lk * kv_rs + head * HD);
+  const char* vb_ = reinterpret_cast<const char*>(v + (size_t)s * Lk * kv_rs + head * HD);
+  const uint32_t rowB = (uint32_t)kv_rs * 2u;
   auto stage = [&](int buf, int kt) {
     char* b = smem + buf * BUF;
-    stage_rows<HD>(kb_, rowB, kt * B_T, L - 1, b, wid, lane);
-    stage_rows<HD>(vb_, rowB, kt * B_T, L - 1, b + TILE, wid, lane);
+    stage_rows<HD>(kb_, rowB, kt * B_T, Lk - 1, b, wid, lane);
+    stage_rows<HD>(vb_, rowB, kt * B_T, Lk - 1, b + TILE, wid, lane);
   };
 
   f16v dqt[NDB];  // dQ^T [d x q] in 32-row d blocks
@@ -189,8 +193,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq(const bf16_t* __restrict__
           dqt[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_tr(tk, db, kb, j, lane), dsb[kb][j], dqt[db], 0, 0, 0);  // dQ^T += K^T dS^T
   }
 
-  if (q0 + r < L) {
-    bf16_t* op = dq + ((size_t)s * L + q0 + r) * dq_rs + head * HD;
+  if (q0 + r < Lq) {
+    bf16_t* op = dq + ((size_t)s * Lq + q0 + r) * dq_rs + head * HD;
 #pragma unroll
     for (int db = 0; db < NDB; ++db)
 #pragma unroll
@@ -209,8 +213,9 @@ template <int HD>
 __global__ __launch_bounds__(256, HD == 64 ? 2 : 1) void attn_bwd_dkv(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
                                                        const bf16_t* __restrict__ v, const bf16_t* __restrict__ d_o,
                                                        const float* __restrict__ lse, const float* __restrict__ delta,
-                                                       bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int L, long qkv_rs,
-                                                       long do_rs, long dkv_rs, int heads, int nk, const int* __restrict__ klim) {
+                                                       bf16_t* __restrict__ dk, bf16_t* __restrict__ dv, int Lq, int Lk, long q_rs,
+                                                       long kv_rs, long do_rs, long dkv_rs, int heads, int nk,
+                                                       const int* __restrict__ klim) {
   constexpr int NKS = HD / 16, NDB = HD / 32, TILE = tile_bytes<HD>();
   constexpr int BUF = 2 * TILE + 3 * B_T * 4;  // [Q | dO | lse | delta | key limit]
   __shared__ __attribute__((aligned(16))) char smem[2 * BUF];
@@ -221,45 +226,45 @@ __global__ __launch_bounds__(256, HD == 64 ? 2 : 1) void attn_bwd_dkv(const bf16
   const int sh = t / nk, kt0 = t - sh * nk;
   const int head = sh % heads, s = sh / heads;
   const int k0 = kt0 * 128 + wid * 32;
-  const int krow = min(k0 + r, L - 1);
+  const int krow = min(k0 + r, Lk - 1);
 
   bf8v kf[NKS], vf[NKS];  // B operands: the lane's key, 8 features at 16 ks + 8 hh
   {
-    const bf16_t* kp = k + ((size_t)s * L + krow) * qkv_rs + head * HD + 8 * hh;
-    const bf16_t* vp = v + ((size_t)s * L + krow) * qkv_rs + head * HD + 8 * hh;
+    const bf16_t* kp = k + ((size_t)s * Lk + krow) * kv_rs + head * HD + 8 * hh;
+    const bf16_t* vp = v + ((size_t)s * Lk + krow) * kv_rs + head * HD + 8 * hh;
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
       kf[ks] = *reinterpret_cast<const bf8v*>(kp + 16 * ks);
       vf[ks] = *reinterpret_cast<const bf8v*>(vp + 16 * ks);
     }
   }
-  const char* qb_ = reinterpret_cast<const char*>(q + (size_t)s * L * qkv_rs + head * HD);
-  const char* ob_ = reinterpret_cast<const char*>(d_o + (size_t)s * L * do_rs + head * HD);
-  const float* lse_b = lse + ((size_t)s * heads + head) * L;
-  const float* del_b = delta + ((size_t)s * heads + head) * L;
-  const uint32_t qB = (uint32_t)qkv_rs * 2u, oB = (uint32_t)do_rs * 2u;
+  const char* qb_ = reinterpret_cast<const char*>(q + (size_t)s * Lq * q_rs + head * HD);
+  const char* ob_ = reinterpret_cast<const char*>(d_o + (size_t)s * Lq * do_rs + head * HD);
+  const float* lse_b = lse + ((size_t)s * heads + head) * Lq;
+  const float* del_b = delta + ((size_t)s * heads + head) * Lq;
+  const uint32_t qB = (uint32_t)q_rs * 2u, oB = (uint32_t)do_rs * 2u;
   auto stage = [&](int buf, int qt) {
     char* b = smem + buf * BUF;
-    stage_rows<HD>(qb_, qB, qt * B_T, L - 1, b, wid, lane);
-    stage_rows<HD>(ob_, oB, qt * B_T, L - 1, b + TILE, wid, lane);
+    stage_rows<HD>(qb_, qB, qt * B_T, Lq - 1, b, wid, lane);
+    stage_rows<HD>(ob_, oB, qt * B_T, Lq - 1, b + TILE, wid, lane);
     if (tid < 3 * B_T) {  // the tile's lse | delta | key limit (plain stores: visible after the barrier that opens the tile)
       const int i = tid & (B_T - 1);
-      const int row = min(qt * B_T + i, L - 1);
+      const int row = min(qt * B_T + i, Lq - 1);
       if (tid < 2 * B_T) reinterpret_cast<float*>(b + 2 * TILE)[tid] = tid < B_T ? lse_b[row] : del_b[row];
-      else reinterpret_cast<int*>(b + 2 * TILE)[tid] = (qt * B_T + i) >= L ? 0 : (klim ? klim[row] : L);  // queries past L see no key
+      else reinterpret_cast<int*>(b + 2 * TILE)[tid] = (qt * B_T + i) >= Lq ? 0 : (klim ? klim[row] : Lk);  // queries past Lq see no key
     }
   };
 
   f16v dkt[NDB], dvt[NDB];  // dK^T, dV^T [d x key] in 32-row d blocks
 #pragma unroll
   for (int db = 0; db < NDB; ++db) dkt[db] = dvt[db] = zero16();
-  const int nqt = (L + B_T - 1) / B_T;
+  const int nqt = (Lq + B_T - 1) / B_T;
   // masked: query tiles whose largest limit does not reach this workgroup's first key contribute nothing (klim is non-decreasing,
   // so they form a prefix of the tile list)
   int qt_first = 0;
   if (klim) {
     const int key_first = kt0 * 128;
-    while (qt_first < nqt - 1 && klim[min(qt_first * B_T + B_T - 1, L - 1)] <= key_first) ++qt_first;
+    while (qt_first < nqt - 1 && klim[min(qt_first * B_T + B_T - 1, Lq - 1)] <= key_first) ++qt_first;
   }
   const int key_lane = k0 + r;  // the lane's key
   stage(qt_first & 1, qt_first);
@@ -307,9 +312,9 @@ __global__ __launch_bounds__(256, HD == 64 ? 2 : 1) void attn_bwd_dkv(const bf16
         }
   }
 
-  if (k0 + r < L) {
-    bf16_t* kp = dk + ((size_t)s * L + k0 + r) * dkv_rs + head * HD;
-    bf16_t* vp = dv + ((size_t)s * L + k0 + r) * dkv_rs + head * HD;
+  if (k0 + r < Lk) {  // keys past Lk are never stored (a limit above Lk, which the contract excludes, reaches no further)
+    bf16_t* kp = dk + ((size_t)s * Lk + k0 + r) * dkv_rs + head * HD;
+    bf16_t* vp = dv + ((size_t)s * Lk + k0 + r) * dkv_rs + head * HD;
 #pragma unroll
     for (int db = 0; db < NDB; ++db)
 #pragma unroll
@@ -325,7 +330,7 @@ __global__ __launch_bounds__(256, HD == 64 ? 2 : 1) void attn_bwd_dkv(const bf16
 
 // delta[s, head, l] = sum_c dO[s, l, head, c] * O[s, l, head, c]: 16 lanes per (token, head), 16 bytes each (HD / 8 of them active)
 __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* __restrict__ d_o, const bf16_t* __restrict__ o,
-                                                         float* __restrict__ delta, int L, int heads, int hd, long do_rs, long o_rs,
+                                                         float* __restrict__ delta, int Lq, int heads, int hd, long do_rs, long o_rs,
                                                          long total) {
   const long i = (long)blockIdx.x * 16 + (threadIdx.x >> 4);  // (s, l, head) index, head fastest
   const int part = threadIdx.x & 15;
@@ -335,8 +340,8 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* __restric
   if (i < total) {
     head = (int)(i % heads);
     const long sl = i / heads;
-    l = (int)(sl % L);
-    s = sl / L;
+    l = (int)(sl % Lq);
+    s = sl / Lq;
     if (part * 8 < hd) {
       const u4v a = *reinterpret_cast<const u4v*>(d_o + sl * do_rs + head * hd + part * 8);
       const u4v b = *reinterpret_cast<const u4v*>(o + sl * o_rs + head * hd + part * 8);
@@ -349,33 +354,40 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* __restric
   acc += dpp_move<0x4e>(acc);   // xor 2
   acc += dpp_move<0x141>(acc);  // i <-> 7 - i
   acc += dpp_move<0x140>(acc);  // i <-> 15 - i: completes the 16-lane sum
-  if (i < total && part == 0) delta[(s * heads + head) * L + l] = acc;
+  if (i < total && part == 0) delta[(s * heads + head) * Lq + l] = acc;
 }
 
 int attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse, float* delta, void* dq,
-             void* dk, void* dv, int S, int heads, int L, int hd, long qkv_rs, long o_rs, long do_rs, long dqkv_rs, float scale,
-             hipStream_t st, const int* klim) {
-  if (S <= 0 || L <= 0) return 0;
+             void* dk, void* dv, int S, int heads, int Lq, int Lk, int hd, long q_rs, long kv_rs, long o_rs, long do_rs, long dq_rs,
+             long dkv_rs, float scale, hipStream_t st, const int* klim) {
+  if (S <= 0 || Lq <= 0) return 0;
   if (heads <= 0) return set_error(NOVA_ERR_SHAPE, "attn_bwd: bad heads");
+  if (Lk <= 0) return set_error(NOVA_ERR_SHAPE, "attn_bwd: bad Lk");
   if (hd != 64 && hd != 96) return set_error(NOVA_ERR_SHAPE, "attn_bwd: head_dim %d not built (have 64 and 96)", hd);
-  if (qkv_rs % 8 || do_rs % 8 || dqkv_rs % 8 || o_rs % 8) return set_error(NOVA_ERR_SHAPE, "attn_bwd: row strides must be 16-byte multiples");
-  if ((long)L * qkv_rs * 2 > 0x7fffffffL || (long)L * do_rs * 2 > 0x7fffffffL) return set_error(NOVA_ERR_SHAPE, "attn_bwd: a sequence's rows must span < 2 GiB");
-  const int nt = (L + 127) / 128;
-  const long blocks = (long)nt * heads * S;
-  if (blocks > 0x7fffffffL) return set_error(NOVA_ERR_SHAPE, "attn_bwd: grid too large");
+  if (q_rs % 8 || kv_rs % 8 || do_rs % 8 || dq_rs % 8 || dkv_rs % 8 || o_rs % 8) return set_error(NOVA_ERR_SHAPE, "attn_bwd: row strides must be 16-byte multiples");
+  // the streamed tiles are addressed with 32-bit byte offsets from a sequence's first row: one check per streamed side
+  if ((long)Lq * q_rs * 2 > 0x7fffffffL || (long)Lq * do_rs * 2 > 0x7fffffffL || (long)Lk * kv_rs * 2 > 0x7fffffffL)
+    return set_error(NOVA_ERR_SHAPE, "attn_bwd: a sequence's rows must span < 2 GiB");
+  const int nq = (Lq + 127) / 128, nk = (Lk + 127) / 128;
+  const long qblocks = (long)nq * heads * S, kblocks = (long)nk * heads * S;
+  if (qblocks > 0x7fffffffL || kblocks > 0x7fffffffL) return set_error(NOVA_ERR_SHAPE, "attn_bwd: grid too large");
   const bf16_t *qq = (const bf16_t*)q, *kk = (const bf16_t*)k, *vv = (const bf16_t*)v, *oo = (const bf16_t*)d_o;
-  const long rows = (long)S * L * heads;
-  hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, oo, (const bf16_t*)o, delta, L, heads, hd,
+  const long rows = (long)S * Lq * heads;
+  if ((rows + 15) / 16 > 0x7fffffffL) return set_error(NOVA_ERR_SHAPE, "attn_bwd: grid too large");
+  hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, st, oo, (const bf16_t*)o, delta, Lq, heads, hd,
                      do_rs, o_rs, rows);
-  const dim3 grid((unsigned)blocks), block(256);
+  // one workgroup per 128 query rows (dq) and per 128 key rows (dk, dv): two grids once the lengths differ
+  const dim3 qgrid((unsigned)qblocks), kgrid((unsigned)kblocks), block(256);
   if (hd == 64) {
-    hipLaunchKernelGGL(attn_bwd_dq<64>, grid, block, 0, st, qq, kk, vv, oo, lse, delta, (bf16_t*)dq, L, qkv_rs, do_rs, dqkv_rs, scale, heads, nt, klim);
-    hipLaunchKernelGGL(attn_bwd_dkv<64>, grid, block, 0, st, qq, kk, vv, oo, lse, delta, (bf16_t*)dk, (bf16_t*)dv, L, qkv_rs, do_rs, dqkv_rs,
-                       heads, nt, klim);
+    hipLaunchKernelGGL(attn_bwd_dq<64>, qgrid, block, 0, st, qq, kk, vv, oo, lse, delta, (bf16_t*)dq, Lq, Lk, q_rs, kv_rs, do_rs, dq_rs, scale,
+                       heads, nq, klim);
+    hipLaunchKernelGGL(attn_bwd_dkv<64>, kgrid, block, 0, st, qq, kk, vv, oo, lse, delta, (bf16_t*)dk, (bf16_t*)dv, Lq, Lk, q_rs, kv_rs, do_rs,
+                       dkv_rs, heads, nk, klim);
   } else {
-    hipLaunchKernelGGL(attn_bwd_dq<96>, grid, block, 0, st, qq, kk, vv, oo, lse, delta, (bf16_t*)dq, L, qkv_rs, do_rs, dqkv_rs, scale, heads, nt, klim);
-    hipLaunchKernelGGL(attn_bwd_dkv<96>, grid, block, 0, st, qq, kk, vv, oo, lse, delta, (bf16_t*)dk, (bf16_t*)dv, L, qkv_rs, do_rs, dqkv_rs,
-                       heads, nt, klim);
+    hipLaunchKernelGGL(attn_bwd_dq<96>, qgrid, block, 0, st, qq, kk, vv, oo, lse, delta, (bf16_t*)dq, Lq, Lk, q_rs, kv_rs, do_rs, dq_rs, scale,
+                       heads, nq, klim);
+    hipLaunchKernelGGL(attn_bwd_dkv<96>, kgrid, block, 0, st, qq, kk, vv, oo, lse, delta, (bf16_t*)dk, (bf16_t*)dv, Lq, Lk, q_rs, kv_rs, do_rs,
+                       dkv_rs, heads, nk, klim);
   }
   return check_launch("attn_bwd");
 }

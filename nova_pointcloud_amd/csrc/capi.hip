@@ -189,8 +189,30 @@ int nova_attn_bwd(const void* q_scaled, const void* k, const void* v, const void
                   long qkv_row_stride, long o_row_stride, long do_row_stride, long dqkv_row_stride, float scale,
                   const int* key_limit, void* stream) {
   NOVA_REQUIRE(q_scaled && k && v && o && d_o && lse && delta_scratch && dq && dk && dv, NOVA_ERR_ARG, "attn_bwd: null pointer");
-  return attn_bwd(q_scaled, k, v, o, d_o, lse, delta_scratch, dq, dk, dv, S, heads, L, head_dim, qkv_row_stride, o_row_stride,
-                  do_row_stride, dqkv_row_stride, scale, (hipStream_t)stream, key_limit);
+  return attn_bwd(q_scaled, k, v, o, d_o, lse, delta_scratch, dq, dk, dv, S, heads, L, L, head_dim, qkv_row_stride, qkv_row_stride,
+                  o_row_stride, do_row_stride, dqkv_row_stride, dqkv_row_stride, scale, (hipStream_t)stream, key_limit);
+}
+
+int nova_attn_cross_fwd_lse(const void* q_scaled, const void* k, const void* v, void* o, float* lse, int S, int heads, int Lq, int Lk,
+                            int head_dim, long q_row_stride, long kv_row_stride, long o_row_stride, const int* key_limit,
+                            void* stream) {
+  NOVA_REQUIRE(q_scaled && k && v && o && lse, NOVA_ERR_ARG, "attn_cross_fwd_lse: null pointer");
+  if (S <= 0 || Lq <= 0) return 0;
+  // the kernels address a sequence's rows with 32-bit byte offsets
+  NOVA_REQUIRE((long)Lq * q_row_stride * 2 <= 0x7fffffffL && (long)Lq * o_row_stride * 2 <= 0x7fffffffL &&
+                   (long)Lk * kv_row_stride * 2 <= 0x7fffffffL,
+               NOVA_ERR_SHAPE, "attn_cross_fwd_lse: a sequence's rows must span < 2 GiB");
+  return attn_fwd(q_scaled, k, v, o, S, heads, Lq, Lk, head_dim, q_row_stride, kv_row_stride, o_row_stride, 1.0f, NOVA_BF16,
+                  (hipStream_t)stream, true, 0, lse, key_limit);
+}
+
+int nova_attn_cross_bwd(const void* q_scaled, const void* k, const void* v, const void* o, const void* d_o, const float* lse,
+                        float* delta_scratch, void* dq, void* dk, void* dv, int S, int heads, int Lq, int Lk, int head_dim,
+                        long q_row_stride, long kv_row_stride, long o_row_stride, long do_row_stride, long dq_row_stride,
+                        long dkv_row_stride, float scale, const int* key_limit, void* stream) {
+  NOVA_REQUIRE(q_scaled && k && v && o && d_o && lse && delta_scratch && dq && dk && dv, NOVA_ERR_ARG, "attn_cross_bwd: null pointer");
+  return attn_bwd(q_scaled, k, v, o, d_o, lse, delta_scratch, dq, dk, dv, S, heads, Lq, Lk, head_dim, q_row_stride, kv_row_stride,
+                  o_row_stride, do_row_stride, dq_row_stride, dkv_row_stride, scale, (hipStream_t)stream, key_limit);
 }
 
 int nova_row_norm(const void* in, void* out, const float* gamma, const float* beta, const void* mod, long mod_ld,

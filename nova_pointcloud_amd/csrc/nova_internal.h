@@ -133,11 +133,13 @@ int attn_fwd_m16(const AttnFwdArgs& a, AttnForm f);  // attn16.hip; attn_fwd che
 int attn_set_variant(int v);  // -1 default, 0 .. 5 (attn.hip); -1 returned for other values
 int attn_variant();
 // attn_bwd.hip (bf16, head_dim 64 / 96): gradients of the attention above from q (pre-scaled by scale * log2 e), k, v, the
-// forward's output o and log2-domain row log-sum-exp, and dO; delta [S, heads, L] is scratch (filled with sum_c dO * O first).
-// All matrices token-major [S, L, heads * hd] with row strides.
+// forward's output o and log2-domain row log-sum-exp, and dO; delta [S, heads, Lq] is scratch (filled with sum_c dO * O first).
+// All matrices token-major with row strides: q, o, dO, dq [S, Lq, heads * hd]; k, v, dk, dv [S, Lk, heads * hd]. Self-attention
+// is Lq == Lk with q_rs == kv_rs and dq_rs == dkv_rs (nova_attn_bwd); nova_attn_cross_bwd passes them apart.
 int attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse, float* delta, void* dq,
-             void* dk, void* dv, int S, int heads, int L, int hd, long qkv_rs, long o_rs, long do_rs, long dqkv_rs, float scale,
-             hipStream_t st, const int* klim = nullptr);  // klim [L]: optional per-query key limit (block-causal frame mask)
+             void* dk, void* dv, int S, int heads, int Lq, int Lk, int hd, long q_rs, long kv_rs, long o_rs, long do_rs, long dq_rs,
+             long dkv_rs, float scale, hipStream_t st,
+             const int* klim = nullptr);  // klim [Lq]: optional per-query key limit in [1, Lk], non-decreasing
 
 // ---- rowops.hip
 struct RowNormArgs {

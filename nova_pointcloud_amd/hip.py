@@ -123,6 +123,8 @@ SIGNATURES = {
     "nova_modulate_rows": [c_void_p] * 3 + [c_long, c_int, c_int, c_void_p],
     "nova_attn_fwd_lse": [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_long, c_long, c_void_p, c_void_p],
     "nova_attn_bwd": [c_void_p] * 10 + [c_int, c_int, c_int, c_int, c_long, c_long, c_long, c_long, c_float, c_void_p, c_void_p],
+    "nova_attn_cross_fwd_lse": [c_void_p] * 5 + [c_int] * 5 + [c_long] * 3 + [c_void_p, c_void_p],
+    "nova_attn_cross_bwd": [c_void_p] * 10 + [c_int] * 5 + [c_long] * 6 + [c_float, c_void_p, c_void_p],
     "nova_row_norm_bwd": [c_void_p] * 5 + [c_long, c_int, c_int, c_int] + [c_void_p] * 4 + [c_int, c_long, c_int, c_float, c_int, c_void_p],
     "nova_act_fwd": [c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p],
     "nova_act_bwd": [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_int, c_int, c_void_p],
