@@ -1,7 +1,9 @@
 """What the point-set modules (metrics, losses, sampling, neighbors, clustering) share on the host side: the checks of
 point tensors and of the arguments several operations take, the split of a cloud set into launches with the one loop
-that sends them out, and the body of the two sampling functions that exist with and without a gradient. Private to the
+that sends them out, and the body of the two sampling functions that exist with and without a gradient; and what the fused training ops (point_embed, point_head, encoding, clustering,
+dropout) share: their argument checks, their sizing and the sums over the clouds that end their backwards. Private to the
 package; metrics re-exports the names its tests and tools use."""
+import contextlib
 import math
 
 import numpy as np
@@ -68,9 +70,9 @@ def _at_least_one(v, name):
     return v
 
 
-def _check_clamp(clamp):
+def _check_clamp(clamp, name="clamp"):
     if clamp is not None and not (isinstance(clamp, (int, float)) and not isinstance(clamp, bool) and 0 < clamp < math.inf):
-        raise ValueError(f"clamp must be None or a positive finite number, got {clamp!r}")
+        raise ValueError(f"{name} must be None or a positive finite number, got {clamp!r}")
     return (-float(clamp), float(clamp)) if clamp is not None else (-math.inf, math.inf)
 
 
@@ -116,6 +118,75 @@ def _launching(device, n_clouds, per):
 def _at(t, s0):
     """The device address of cloud s0 of the per-cloud tensor t; NULL for an argument that is not there (None)."""
     return t[s0].data_ptr() if t is not None else None
+
+
+# ---- the fused training ops (point_embed, point_head, encoding, clustering, dropout): their argument checks, each a step of
+# its own over all of `named`, a sequence of (tensor, name), so a module can put a check of its own between two of them
+
+MAX_CLOUDS_PER_CALL = 65535  # clouds go in grid.y
+
+
+def _all_tensors(named):
+    for t, name in named:
+        if not torch.is_tensor(t):
+            raise ValueError(f"{name}: expected a tensor, got {type(t).__name__}")
+
+
+def _all_floating(named):
+    for t, name in named:
+        if not t.is_floating_point():
+            raise ValueError(f"{name}: expected a floating dtype, got {t.dtype}")
+
+
+def _same_device(named):
+    """Every entry is on the device of the first."""
+    first, lead = named[0]
+    for t, name in named[1:]:
+        if t.device != first.device:
+            raise ValueError(f"{lead} and {name} must be on the same device, got {first.device} and {t.device}")
+
+
+def _on_gpu(named, what):
+    """NovaHipError for a CPU tensor (an entry that is None is skipped); `what` is what runs on the GPU, "the point head"."""
+    for t, name in named:
+        if t is not None and not t.is_cuda:
+            raise hip.NovaHipError(f"{name}: {what} runs on the GPU (got a CPU tensor)")
+
+
+def _chunks(N, chunk):
+    return (N + chunk - 1) // chunk
+
+
+def _budget_clouds_per_launch(budget, cost):
+    """The default clouds per launch: what fits the module's per-launch budget at `cost` per cloud, 1 .. MAX_CLOUDS_PER_CALL."""
+    return max(1, min(budget // cost, MAX_CLOUDS_PER_CALL))
+
+
+def _allocator(n_clouds, device):
+    """new(*shape, dtype=torch.float32) for what a backward's launches write. An empty cloud set launches nothing, so nothing
+    writes a sum over the clouds: there it starts from +0 and stays there."""
+    make = torch.empty if n_clouds > 0 else torch.zeros
+    return lambda *shape, dtype=torch.float32: make(*shape, dtype=dtype, device=device)
+
+
+@contextlib.contextmanager
+def _launch_stream(device, n_clouds, per):
+    """The launch loop of a backward whose sums over the clouds follow it on the same device and stream (_launching leaves
+    the device after the last step): `with _launch_stream(x.device, S, per) as (stream, spans)` holds `device` current, with
+    `stream` its current stream, read once, and `spans` what _launches gives."""
+    spans = _launches(n_clouds, per)
+    with torch.cuda.device(device):
+        yield hip.stream_ptr(), spans
+
+
+def _sum_over(entry, parts, count, out_shape, *extra, stream, stats, key):
+    """float32 `out_shape`: the `count` leading slices of `parts` added from +0 in ascending order by the entry point
+    `entry`(parts, out, count, *extra, stream), counted in stats[key]. count == 0 launches nothing and gives +0."""
+    out = (torch.empty if count > 0 else torch.zeros)(out_shape, dtype=torch.float32, device=parts.device)
+    if count > 0:
+        hip.call(entry, parts.data_ptr(), out.data_ptr(), count, *extra, stream)
+        stats[key] += 1
+    return out
 
 
 INTERP_MAX_POINTS = 65536  # == NOVA_INTERP_MAX_POINTS of include/nova_hip.h

@@ -15,12 +15,12 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import hip
-from ._pointset import _at, _clouds_per_launch, _interp_scale, _launches, _launching
+from ._pointset import (MAX_CLOUDS_PER_CALL, _all_floating, _all_tensors, _allocator, _at, _budget_clouds_per_launch, _chunks, _clouds_per_launch,
+                        _interp_scale, _launch_stream, _launching, _on_gpu, _same_device, _sum_over)
 
 SOFT_CLUSTER_MAX_POINTS = 65536  # == NOVA_SOFT_CLUSTER_MAX_POINTS of include/nova_hip.h
 SOFT_CLUSTER_MAX_K = 32  # == NOVA_SOFT_CLUSTER_MAX_K
 SOFT_CLUSTER_CHUNK = 1024  # == NOVA_SOFT_CLUSTER_CHUNK: points per workgroup, the unit of the workspace
-_MAX_CLOUDS_PER_CALL = 65535  # clouds go in grid.y
 # Per-launch budget, ESTIMATED BY COUNT, not from a measured time: (point, centre) pairs a launch forms, about 40 issue slots
 # each forward and 80 backward; 2^31 pairs are a few milliseconds on 256 compute units.
 _SOFT_CLUSTER_PAIRS_PER_LAUNCH = 1 << 31
@@ -31,23 +31,12 @@ _SOFT_CLUSTER_PAIRS_PER_LAUNCH = 1 << 31
 stats = {"forward_launches": 0, "point_grad_launches": 0, "center_grad_launches": 0, "cloud_sum_launches": 0}
 
 
-def _default_clouds_per_launch(N, K):
-    return max(1, min(_SOFT_CLUSTER_PAIRS_PER_LAUNCH // (N * K), _MAX_CLOUDS_PER_CALL))
-
-
-def _chunks(N):
-    return (N + SOFT_CLUSTER_CHUNK - 1) // SOFT_CLUSTER_CHUNK
-
-
 def _pool_arguments(points, centers):
     """ValueError for everything about the tensors that does not need the GPU (so it holds for CPU tensors too), in one
     order: types, dtypes, shapes, cloud counts, ranges, device."""
-    for t, name in ((points, "points"), (centers, "centers")):
-        if not torch.is_tensor(t):
-            raise ValueError(f"{name}: expected a tensor, got {type(t).__name__}")
-    for t, name in ((points, "points"), (centers, "centers")):
-        if not t.is_floating_point():
-            raise ValueError(f"{name}: expected a floating dtype, got {t.dtype}")
+    given = ((points, "points"), (centers, "centers"))
+    _all_tensors(given)
+    _all_floating(given)
     if points.dim() != 3 or points.shape[-1] != 3:
         raise ValueError(f"points: expected [S, N, 3] clouds, got {tuple(points.shape)}")
     if centers.dim() not in (2, 3) or centers.shape[-1] != 3:
@@ -59,8 +48,7 @@ def _pool_arguments(points, centers):
         raise ValueError(f"points: the soft-cluster kernel takes 1 .. {SOFT_CLUSTER_MAX_POINTS} points per cloud, got {N}")
     if not 1 <= K <= SOFT_CLUSTER_MAX_K:
         raise ValueError(f"centers: the soft-cluster kernel takes 1 .. {SOFT_CLUSTER_MAX_K} centres, got {K}")
-    if points.device != centers.device:
-        raise ValueError(f"points and centers must be on the same device, got {points.device} and {centers.device}")
+    _same_device(given)
 
 
 class _SoftCluster(torch.autograd.Function):
@@ -70,7 +58,7 @@ class _SoftCluster(torch.autograd.Function):
         K, shared = c.shape[-2], c.dim() == 2
         out = torch.empty(S, K, 3, dtype=torch.float32, device=x.device)
         mass = torch.empty(S, K, dtype=torch.float32, device=x.device)
-        ws = torch.empty(min(S, per) * _chunks(N) * K * 4, dtype=torch.float32, device=x.device)  # one launch's chunk partials
+        ws = torch.empty(min(S, per) * _chunks(N, SOFT_CLUSTER_CHUNK) * K * 4, dtype=torch.float32, device=x.device)  # one launch's chunk partials
         for stream, s0, count in _launching(x.device, S, per):
             hip.call("nova_pointset_soft_cluster", _at(x, s0), c.data_ptr() if shared else _at(c, s0), _at(out, s0), _at(mass, s0),
                      ws.data_ptr(), count, N, K, 1 if shared else 0, scale, stream)
@@ -92,24 +80,19 @@ class _SoftCluster(torch.autograd.Function):
             return None, None, None, None
         g = torch.zeros_like(out) if g is None else g.float().contiguous()
         gm = gm.float().contiguous() if gm is not None else None
-        gx = torch.empty_like(x) if want_x else None
-        gc = torch.empty(S, K, 3, dtype=torch.float32, device=x.device) if want_c else None  # per cloud in both centre forms
-        ws = torch.empty(min(S, per) * _chunks(N) * K * 3, dtype=torch.float32, device=x.device) if want_c else None
-        # written out, not _launching: the sum over the clouds follows the loop on the same device and stream
-        with torch.cuda.device(x.device):
-            stream = hip.stream_ptr()
-            for s0, count in _launches(S, per):
+        new = _allocator(S, x.device)
+        gx = new(S, N, 3) if want_x else None
+        gc = new(S, K, 3) if want_c else None  # per cloud in both centre forms
+        ws = new(min(S, per) * _chunks(N, SOFT_CLUSTER_CHUNK) * K * 3) if want_c else None
+        with _launch_stream(x.device, S, per) as (stream, spans):
+            for s0, count in spans:
                 hip.call("nova_pointset_soft_cluster_bwd", _at(x, s0), c.data_ptr() if shared else _at(c, s0), _at(out, s0), _at(mass, s0),
                          _at(g, s0), _at(gm, s0), _at(gx, s0), _at(gc, s0), ws.data_ptr() if want_c else None, count, N, K, 1 if shared else 0,
                          scale, stream)
                 stats["point_grad_launches"] += 1 if want_x else 0
                 stats["center_grad_launches"] += 1 if want_c else 0
             if want_c and shared:  # after every launch has written its clouds: ascending cloud order, whatever the split
-                gcs = torch.zeros(K, 3, dtype=torch.float32, device=x.device)
-                if S > 0:
-                    hip.call("nova_pointset_soft_cluster_sum_clouds", gc.data_ptr(), gcs.data_ptr(), S, K, stream)
-                    stats["cloud_sum_launches"] += 1
-                gc = gcs
+                gc = _sum_over("nova_pointset_soft_cluster_sum_clouds", gc, S, (K, 3), K, stream=stream, stats=stats, key="cloud_sum_launches")
         return gx, gc, None, None
 
 
@@ -135,10 +118,9 @@ def soft_cluster_pool(points, centers, temperature=1.0, return_mass=False, max_c
     max_clouds_per_launch. NovaHipError for CPU tensors."""
     _pool_arguments(points, centers)
     scale = _interp_scale(temperature)
-    per = _clouds_per_launch(max_clouds_per_launch, _default_clouds_per_launch(points.shape[1], centers.shape[-2]), _MAX_CLOUDS_PER_CALL)
-    for t, name in ((points, "points"), (centers, "centers")):
-        if not t.is_cuda:
-            raise hip.NovaHipError(f"{name}: the soft cluster pooling runs on the GPU (got a CPU tensor)")
+    per = _clouds_per_launch(max_clouds_per_launch, _budget_clouds_per_launch(_SOFT_CLUSTER_PAIRS_PER_LAUNCH, points.shape[1] * centers.shape[-2]),
+                             MAX_CLOUDS_PER_CALL)
+    _on_gpu(((points, "points"), (centers, "centers")), "the soft cluster pooling")
     xs = points.float().contiguous()
     cs = centers.float().contiguous()
     out, mass = _SoftCluster.apply(xs, cs, scale, per)

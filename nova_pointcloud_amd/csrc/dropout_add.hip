@@ -27,7 +27,7 @@
 //     evaluation: the same draws for the same elements, the same bits.
 // Cost per element (counted): one Philox evaluation is 20 32 x 32 -> 64-bit multiplies for 4 elements; the
 // compiler forms each round's two products as full 64-bit ones, so the high and the low word cost one multiply together.
-#include "pointset_common.h"
+#include "fused_common.h"
 
 #pragma clang fp contract(off)  // every rounding below is written out; nothing is fused behind the text
 
@@ -242,7 +242,7 @@ static unsigned da_gcd(unsigned a, unsigned b) {
 
 // checks 2, 3 (without the residual) and 5 .. 7 of the order include/nova_hip.h states, shared by both entries
 static int da_check_head(const char* who, int dtype, int act) {
-  if (bad_dtype(dtype)) return set_error(NOVA_ERR_ARG, "%s: unknown dtype code %d (NOVA_F32, NOVA_BF16, NOVA_F16)", who, dtype);
+  NOVA_REQUIRE(!bad_dtype(dtype), NOVA_ERR_ARG, "%s: unknown dtype code %d (NOVA_F32, NOVA_BF16, NOVA_F16)", who, dtype);
   NOVA_REQUIRE(act == NOVA_DROPOUT_ACT_NONE || act == NOVA_DROPOUT_ACT_RELU, NOVA_ERR_ARG,
                "%s: unknown act code %d (NOVA_DROPOUT_ACT_NONE, NOVA_DROPOUT_ACT_RELU)", who, act);
   return 0;
@@ -286,16 +286,7 @@ static void da_launch(DaArgs& a, int dtype, bool bwd, bool relu, bool chunked, h
       }
       hipLaunchKernelGGL((dropout_add_kernel<T, decltype(b)::value, decltype(r)::value, decltype(w)::value, false>), grid, dim3(DA_T), 0, st, a);
     };
-    auto with_wide = [&](auto b, auto r) {
-      if (wide) go(b, r, std::true_type{});
-      else go(b, r, std::false_type{});
-    };
-    auto with_relu = [&](auto b) {
-      if (relu) with_wide(b, std::true_type{});
-      else with_wide(b, std::false_type{});
-    };
-    if (bwd) with_relu(std::true_type{});
-    else with_relu(std::false_type{});
+    dispatch_flag(bwd, [&](auto b) { dispatch_flag(relu, [&](auto r) { dispatch_flag(wide, [&](auto w) { go(b, r, w); }); }); });
     return 0;
   });
 }
@@ -320,7 +311,7 @@ int nova_bias_dropout_add(const void* x, int dtype, const float* bias, const voi
   const void* ins[3] = {x, bias, residual};
   const size_t nins[3] = {n, (size_t)D * 4, n};
   const char* names[3] = {"x", "bias", "residual"};
-  for (int b = 0; b < 3; ++b) NOVA_REQUIRE(!ranges_overlap(out, n, ins[b], nins[b]), NOVA_ERR_ARG, "%s: out overlaps the input %s", who, names[b]);
+  NOVA_TRY(check_no_overlap(who, out, n, "out", ins, nins, names, 3));
   DaArgs a{x, residual, bias, out, nullptr, rows, first_row, D, 0, T, subsequence, (uint32_t)seed, (uint32_t)(seed >> 32), scale, 0};
   da_launch(a, dtype, false, act == NOVA_DROPOUT_ACT_RELU, false, (hipStream_t)stream);
   return check_launch(who);
@@ -341,13 +332,12 @@ int nova_bias_dropout_add_bwd(const void* g, const void* out, int dtype, void* g
   const bool relu = act == NOVA_DROPOUT_ACT_RELU;
   const size_t n = (size_t)rows * D * esize(dtype), np = (size_t)((rows + DA_CHUNK - 1) / DA_CHUNK) * D * 4;
   const void* ins[2] = {g, relu ? out : nullptr};  // out is not read without an activation
+  const size_t nins[2] = {n, n};
   const char* names[2] = {"g", "out"};
   const void* outs[2] = {gx, gbias_parts};
   const size_t nouts[2] = {n, np};
   const char* onames[2] = {"gx", "gbias_parts"};
-  for (int o = 0; o < 2; ++o)
-    for (int b = 0; b < 2; ++b)
-      NOVA_REQUIRE(!ranges_overlap(outs[o], nouts[o], ins[b], n), NOVA_ERR_ARG, "%s: %s overlaps the input %s", who, onames[o], names[b]);
+  for (int o = 0; o < 2; ++o) NOVA_TRY(check_no_overlap(who, outs[o], nouts[o], onames[o], ins, nins, names, 2));  // both against the inputs first
   NOVA_REQUIRE(!ranges_overlap(gx, n, gbias_parts, np), NOVA_ERR_ARG, "%s: gx and gbias_parts overlap each other", who);
   DaArgs a{g, relu ? out : nullptr, nullptr, gx, gbias_parts, rows, first_row, D, 0, T, subsequence, (uint32_t)seed, (uint32_t)(seed >> 32), scale, 0};
   da_launch(a, dtype, true, relu, gbias_parts != nullptr, (hipStream_t)stream);

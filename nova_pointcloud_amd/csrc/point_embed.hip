@@ -21,9 +21,10 @@
 //                       E is. Per row the gx terms of the block go through wave_sum and are added, block after block, to the
 //                       row's slot in LDS; the four waves' accumulators are merged in wave order through LDS and the chunk's
 //                       partial goes to the caller's workspace.
-//   embed_merge_kernel  one thread per element of gWs [S, E, C] and gcs [S, E]: the chunk partials in ascending chunk order.
-//   embed_sum_clouds_kernel, embed_pos_bwd_kernel: one thread per element (per 16 bytes), the clouds in ascending order.
-// Where the grid of (rows, clouds) has fewer than EM_FEW_WORKGROUPS workgroups, the forward, and the backward when gx is not
+//   ordered_sum_kernel  (fused_common.h) one thread per element of gWs [S, E, C] and gcs [S, E]: the chunk partials in ascending
+//                       chunk order; and one thread per element of nova_pointset_embed_sum_clouds, the clouds in ascending order.
+//   embed_pos_bwd_kernel  one thread per 16 bytes (per element), the clouds in ascending order.
+// Where the grid of (rows, clouds) has fewer than FEW_WORKGROUPS workgroups, the forward, and the backward when gx is not
 // wanted, put one channel block per workgroup in grid.z: the same lanes, channels and orders, three times the workgroups at
 // E = 768.
 // No atomics. A cloud's results depend on (x[s], W, the addends' rows of that cloud, g[s], N, C, E) alone.
@@ -34,7 +35,7 @@
 // out, pos, base or g), as two 8-byte ones where they start on 8, otherwise as four 4-byte ones. The lane keeps the same
 // channels, so the values are the same. Loads of channels past E - 1 are made at channel 0 and not used (no branch around a
 // load); stores there are not made.
-#include "pointset_common.h"
+#include "fused_common.h"
 
 #pragma clang fp contract(off)  // every rounding below is written out; nothing is fused behind the text
 
@@ -48,8 +49,6 @@ constexpr int EM_T = 256;                   // threads per workgroup
 constexpr int EM_WAVES = EM_T / 64;
 constexpr int EM_BLOCK = 256;               // channels per block: four per lane
 constexpr int EM_FWD_ROWS = 64;             // rows per workgroup of the forward (no part of the definition)
-constexpr int EM_FEW_WORKGROUPS = 512;      // below two workgroups per compute unit the channel blocks go to grid.z (likewise)
-constexpr int EM_MERGE_AHEAD = 16;          // partials a thread of the merge and of the cloud sum has in flight (likewise)
 constexpr int EM_AHEAD = 8;                 // rows of g a wave of the backward has in flight (no part of the definition)
 static_assert(EM_CHUNK == 128 && EM_CHUNK % EM_WAVES == 0 && EM_BLOCK == 4 * 64, "the chunk and block shapes are part of the definition");
 
@@ -244,41 +243,6 @@ __global__ __launch_bounds__(EM_T) void embed_bwd_kernel(const float* __restrict
     for (int r = wave; r < rows; r += EM_WAVES) gx[(row0 + r) * C + lane] = gxs[r][lane];
 }
 
-// grid (ceil(E (C + 1) / 256), S): element n of a cloud's partial is gWs[s, n] for n < E C, gcs[s, n - E C] after that
-__global__ __launch_bounds__(EM_T) void embed_merge_kernel(const float* __restrict__ ws, float* __restrict__ gWs, float* __restrict__ gcs,
-                                                           int chunks, int E, int C) {
-  const int n = blockIdx.x * EM_T + threadIdx.x, per = E * (C + 1);
-  if (n >= per) return;
-  const size_t s = blockIdx.y;
-  const bool is_w = n < E * C;
-  if (!(is_w ? gWs : gcs)) return;
-  const float* mine = ws + s * chunks * (size_t)per + n;
-  float total = 0.f;
-  for (int c0 = 0; c0 < chunks; c0 += EM_MERGE_AHEAD) {  // the loads of a group issued together, the additions in order
-    float v[EM_MERGE_AHEAD];
-#pragma unroll
-    for (int u = 0; u < EM_MERGE_AHEAD; ++u) v[u] = mine[(size_t)(c0 + u < chunks ? c0 + u : c0) * per];
-#pragma unroll
-    for (int u = 0; u < EM_MERGE_AHEAD; ++u) total = c0 + u < chunks ? total + v[u] : total;
-  }
-  if (is_w) gWs[s * (size_t)E * C + n] = total;
-  else gcs[s * (size_t)E + (n - E * C)] = total;
-}
-
-__global__ __launch_bounds__(EM_T) void embed_sum_clouds_kernel(const float* __restrict__ per_cloud, float* __restrict__ out, int S, int n) {
-  const int j = blockIdx.x * EM_T + threadIdx.x;
-  if (j >= n) return;
-  float total = 0.f;
-  for (int s0 = 0; s0 < S; s0 += EM_MERGE_AHEAD) {  // the loads of a group issued together, the additions in order
-    float v[EM_MERGE_AHEAD];
-#pragma unroll
-    for (int u = 0; u < EM_MERGE_AHEAD; ++u) v[u] = per_cloud[(size_t)(s0 + u < S ? s0 + u : s0) * n + j];
-#pragma unroll
-    for (int u = 0; u < EM_MERGE_AHEAD; ++u) total = s0 + u < S ? total + v[u] : total;
-  }
-  out[j] = total;
-}
-
 // thread t takes the VEC elements from VEC t on of [N, E] (n = N E, n % VEC == 0)
 template <int VEC>
 __global__ __launch_bounds__(EM_T) void embed_pos_bwd_kernel(const float* __restrict__ g, float* __restrict__ gpos, int S, size_t n, int accumulate) {
@@ -302,10 +266,10 @@ __global__ __launch_bounds__(EM_T) void embed_pos_bwd_kernel(const float* __rest
 
 // the checks the entries share, in the order include/nova_hip.h states: C, E, N, S
 static int em_check(const char* who, int S, int N, int C, int E) {
-  if (C < 1 || C > EM_MAX_C) return set_error(NOVA_ERR_SHAPE, "%s: C %d outside 1 .. %d (NOVA_EMBED_MAX_IN)", who, C, EM_MAX_C);
-  if (E < 1 || E > EM_MAX_E) return set_error(NOVA_ERR_SHAPE, "%s: E %d outside 1 .. %d (NOVA_EMBED_MAX_DIM)", who, E, EM_MAX_E);
-  if (N < 1 || N > EM_MAX_N) return set_error(NOVA_ERR_SHAPE, "%s: N %d outside 1 .. %d (NOVA_EMBED_MAX_POINTS)", who, N, EM_MAX_N);
-  if (S > 65535) return set_error(NOVA_ERR_SHAPE, "%s: %d clouds exceed one launch (65535)", who, S);
+  NOVA_REQUIRE(C >= 1 && C <= EM_MAX_C, NOVA_ERR_SHAPE, "%s: C %d outside 1 .. %d (NOVA_EMBED_MAX_IN)", who, C, EM_MAX_C);
+  NOVA_REQUIRE(E >= 1 && E <= EM_MAX_E, NOVA_ERR_SHAPE, "%s: E %d outside 1 .. %d (NOVA_EMBED_MAX_DIM)", who, E, EM_MAX_E);
+  NOVA_REQUIRE(N >= 1 && N <= EM_MAX_N, NOVA_ERR_SHAPE, "%s: N %d outside 1 .. %d (NOVA_EMBED_MAX_POINTS)", who, N, EM_MAX_N);
+  NOVA_REQUIRE(S <= 65535, NOVA_ERR_SHAPE, "%s: %d clouds exceed one launch (65535)", who, S);
   return 0;
 }
 
@@ -315,23 +279,6 @@ static int em_vec(int E, const void* a, const void* b = nullptr, const void* c =
   return bits % 16 == 0 ? 4 : bits % 8 == 0 ? 2 : 1;
 }
 
-// A small grid (a single cloud, say) leaves compute units idle and every wave waiting on its own loads: there the channel
-// blocks are spread over grid.z, one per workgroup. A block's results do not depend on who computes the others.
-static unsigned em_block_split(int workgroups, int E) { return workgroups < EM_FEW_WORKGROUPS ? (E + EM_BLOCK - 1) / EM_BLOCK : 1; }
-
-// f(integral_constant<int, C>) for the runtime C in 1 .. 8 (em_check has passed)
-template <typename F> static void em_dispatch_c(int C, F&& f) {
-  switch (C) {
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    case 3: f(std::integral_constant<int, 3>{}); break;
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    case 5: f(std::integral_constant<int, 5>{}); break;
-    case 6: f(std::integral_constant<int, 6>{}); break;
-    case 7: f(std::integral_constant<int, 7>{}); break;
-    default: f(std::integral_constant<int, 8>{}); break;
-  }
-}
 template <typename F> static void em_dispatch_vec(int vec, F&& f) {
   if (vec == 4) f(std::integral_constant<int, 4>{});
   else if (vec == 2) f(std::integral_constant<int, 2>{});
@@ -348,20 +295,18 @@ int nova_pointset_embed(const float* x, const float* W, const float* bias, const
                         float* out, int S, int N, int C, int E, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   const char* who = "pointset_embed";
-  if (const int rc = em_check(who, S, N, C, E)) return rc;
+  NOVA_TRY(em_check(who, S, N, C, E));
   if (S <= 0) return 0;
   const size_t no = (size_t)S * N * E * 4;
   const void* ins[6] = {x, W, bias, pos, cond, base};
   const size_t nins[6] = {(size_t)S * N * C * 4, (size_t)E * C * 4, (size_t)E * 4, (size_t)N * E * 4, (size_t)S * E * 4, no};
   const char* names[6] = {"x", "W", "bias", "pos", "cond", "base"};
-  for (int b = 0; b < 2; ++b)  // every addend may be NULL
-    if (!ins[b]) return set_error(NOVA_ERR_ARG, "%s: null pointer %s", who, names[b]);
-  if (!out) return set_error(NOVA_ERR_ARG, "%s: null pointer out", who);
-  for (int b = 0; b < 6; ++b)
-    if (ranges_overlap(out, no, ins[b], nins[b])) return set_error(NOVA_ERR_ARG, "%s: out overlaps the input %s", who, names[b]);
+  for (int b = 0; b < 2; ++b) NOVA_REQUIRE(ins[b], NOVA_ERR_ARG, "%s: null pointer %s", who, names[b]);  // every addend may be NULL
+  NOVA_REQUIRE(out, NOVA_ERR_ARG, "%s: null pointer out", who);
+  NOVA_TRY(check_no_overlap(who, out, no, "out", ins, nins, names, 6));
   const int groups = (N + EM_FWD_ROWS - 1) / EM_FWD_ROWS;
-  const dim3 grid(groups, S, em_block_split(groups * S, E)), block(EM_T);
-  em_dispatch_c(C, [&](auto c) {
+  const dim3 grid(groups, S, few_workgroups_split(groups * S, E, EM_BLOCK)), block(EM_T);
+  dispatch_count8(C, [&](auto c) {
     em_dispatch_vec(em_vec(E, out, pos, base), [&](auto v) {
       hipLaunchKernelGGL((embed_fwd_kernel<decltype(c)::value, decltype(v)::value>), grid, block, 0, st, x, W, bias, pos, cond, base, out, N, E);
     });
@@ -373,57 +318,52 @@ int nova_pointset_embed_bwd(const float* x, const float* W, const float* g, floa
                             int E, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   const char* who = "pointset_embed_bwd";
-  if (const int rc = em_check(who, S, N, C, E)) return rc;
+  NOVA_TRY(em_check(who, S, N, C, E));
   if (S <= 0) return 0;
   const int chunks = (N + EM_CHUNK - 1) / EM_CHUNK;
   const void* ins[3] = {x, W, g};
   const size_t nins[3] = {(size_t)S * N * C * 4, (size_t)E * C * 4, (size_t)S * N * E * 4};
   const char* names[3] = {"x", "W", "g"};
-  for (int b = 0; b < 3; ++b)
-    if (!ins[b]) return set_error(NOVA_ERR_ARG, "%s: null pointer %s", who, names[b]);
-  if (!gx && !gWs && !gcs) return set_error(NOVA_ERR_ARG, "%s: no gradient wanted (gx, gWs and gcs are all NULL)", who);
-  if ((gWs || gcs) && !ws) return set_error(NOVA_ERR_ARG, "%s: gWs and gcs need the workspace ws", who);
+  for (int b = 0; b < 3; ++b) NOVA_REQUIRE(ins[b], NOVA_ERR_ARG, "%s: null pointer %s", who, names[b]);
+  NOVA_REQUIRE(gx || gWs || gcs, NOVA_ERR_ARG, "%s: no gradient wanted (gx, gWs and gcs are all NULL)", who);
+  NOVA_REQUIRE(ws || !(gWs || gcs), NOVA_ERR_ARG, "%s: gWs and gcs need the workspace ws", who);
   const void* outs[4] = {gx, gWs, gcs, gWs || gcs ? ws : nullptr};
   const size_t nouts[4] = {nins[0], (size_t)S * E * C * 4, (size_t)S * E * 4, (size_t)S * chunks * E * (C + 1) * 4};
   const char* onames[4] = {"gx", "gWs", "gcs", "ws"};
-  for (int a = 0; a < 4; ++a) {
-    for (int b = 0; b < 3; ++b)
-      if (ranges_overlap(outs[a], nouts[a], ins[b], nins[b])) return set_error(NOVA_ERR_ARG, "%s: %s overlaps the input %s", who, onames[a], names[b]);
-    for (int b = a + 1; b < 4; ++b)
-      if (ranges_overlap(outs[a], nouts[a], outs[b], nouts[b])) return set_error(NOVA_ERR_ARG, "%s: %s and %s overlap each other", who, onames[a], onames[b]);
-  }
-  const dim3 grid(chunks, S, gx ? 1 : em_block_split(chunks * S, E)), block(EM_T);  // gx sums over the blocks: one workgroup takes them all
+  NOVA_TRY(check_no_overlap(who, outs, nouts, onames, 4, ins, nins, names, 3));
+  const dim3 grid(chunks, S, gx ? 1 : few_workgroups_split(chunks * S, E, EM_BLOCK)), block(EM_T);  // gx sums over the blocks: one workgroup takes them all
   float* part = gWs || gcs ? ws : nullptr;
-  em_dispatch_c(C, [&](auto c) {
+  dispatch_count8(C, [&](auto c) {
     em_dispatch_vec(em_vec(E, g), [&](auto v) {
       hipLaunchKernelGGL((embed_bwd_kernel<decltype(c)::value, decltype(v)::value>), grid, block, 0, st, x, W, g, gx, part, N, E, gWs ? 1 : 0, gcs ? 1 : 0);
     });
   });
-  if (part) hipLaunchKernelGGL(embed_merge_kernel, dim3((E * (C + 1) + EM_T - 1) / EM_T, S), block, 0, st, part, gWs, gcs, chunks, E, C);
+  if (part) ordered_sum(st, part, gWs, gcs, S, chunks, E * (C + 1), E * C);
   return check_launch(who);
 }
 
 int nova_pointset_embed_sum_clouds(const float* per_cloud, float* out, int S, int n, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   const char* who = "pointset_embed_sum_clouds";
-  if (n < 1 || n > EM_MAX_E * EM_MAX_C) return set_error(NOVA_ERR_SHAPE, "%s: n %d outside 1 .. %d (NOVA_EMBED_MAX_DIM * NOVA_EMBED_MAX_IN)", who, n, EM_MAX_E * EM_MAX_C);
+  NOVA_REQUIRE(n >= 1 && n <= EM_MAX_E * EM_MAX_C, NOVA_ERR_SHAPE, "%s: n %d outside 1 .. %d (NOVA_EMBED_MAX_DIM * NOVA_EMBED_MAX_IN)", who, n,
+               EM_MAX_E * EM_MAX_C);
   if (S <= 0) return 0;
-  if (!per_cloud) return set_error(NOVA_ERR_ARG, "%s: null pointer per_cloud", who);
-  if (!out) return set_error(NOVA_ERR_ARG, "%s: null pointer out", who);
-  if (ranges_overlap(out, (size_t)n * 4, per_cloud, (size_t)S * n * 4)) return set_error(NOVA_ERR_ARG, "%s: out overlaps the input per_cloud", who);
-  hipLaunchKernelGGL(embed_sum_clouds_kernel, dim3((n + EM_T - 1) / EM_T), dim3(EM_T), 0, st, per_cloud, out, S, n);
+  NOVA_REQUIRE(per_cloud, NOVA_ERR_ARG, "%s: null pointer per_cloud", who);
+  NOVA_REQUIRE(out, NOVA_ERR_ARG, "%s: null pointer out", who);
+  NOVA_REQUIRE(!ranges_overlap(out, (size_t)n * 4, per_cloud, (size_t)S * n * 4), NOVA_ERR_ARG, "%s: out overlaps the input per_cloud", who);
+  ordered_sum(st, per_cloud, out, nullptr, 1, S, n, n);
   return check_launch(who);
 }
 
 int nova_pointset_embed_pos_bwd(const float* g, float* gpos, int S, int N, int E, int accumulate, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   const char* who = "pointset_embed_pos_bwd";
-  if (const int rc = em_check(who, S, N, 1, E)) return rc;
+  NOVA_TRY(em_check(who, S, N, 1, E));
   if (S <= 0) return 0;
-  if (!g) return set_error(NOVA_ERR_ARG, "%s: null pointer g", who);
-  if (!gpos) return set_error(NOVA_ERR_ARG, "%s: null pointer gpos", who);
+  NOVA_REQUIRE(g, NOVA_ERR_ARG, "%s: null pointer g", who);
+  NOVA_REQUIRE(gpos, NOVA_ERR_ARG, "%s: null pointer gpos", who);
   const size_t n = (size_t)N * E;
-  if (ranges_overlap(gpos, n * 4, g, (size_t)S * n * 4)) return set_error(NOVA_ERR_ARG, "%s: gpos overlaps the input g", who);
+  NOVA_REQUIRE(!ranges_overlap(gpos, n * 4, g, (size_t)S * n * 4), NOVA_ERR_ARG, "%s: gpos overlaps the input g", who);
   const bool wide = n % 4 == 0 && ((uintptr_t)g | (uintptr_t)gpos) % 16 == 0;
   const size_t threads = wide ? n / 4 : n;
   const dim3 grid((unsigned)((threads + EM_T - 1) / EM_T)), block(EM_T);

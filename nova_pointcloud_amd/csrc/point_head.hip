@@ -19,8 +19,9 @@
 //                      outside the row loop: per block a lane holds 8 C weights and 8 C accumulators of gWs, whatever E is. The
 //                      row's C gradients are wave-uniform; gx is 16 bytes per lane and store. The four waves' accumulators are
 //                      merged in wave order through LDS (64 KiB at C = 8) and the chunk's partial goes to the workspace.
-//   head_merge_kernel  one thread per element of gWs [S, C, E] and gbs [S, C]: the chunk partials in ascending chunk order.
-// Where the grid of (rows, clouds) has fewer than HD_FEW_WORKGROUPS workgroups, the forward takes 16 rows per workgroup
+//   ordered_sum_kernel (fused_common.h) one thread per element of gWs [S, C, E] and gbs [S, C]: the chunk partials in ascending
+//                      chunk order. This file defines no summing kernel of its own.
+// Where the grid of (rows, clouds) has fewer than FEW_WORKGROUPS workgroups, the forward takes 16 rows per workgroup
 // instead of 64 and the backward puts one channel block per workgroup in grid.z: the same lanes, channels and orders.
 // No atomics. A cloud's results depend on (x[s], W, bias, g[s], clamp, N, C, E) alone.
 // VEC: a lane's eight channels move in accesses of 16 bytes where the rows start on 16 bytes (E sizeof(T) % 16 == 0 and
@@ -28,7 +29,7 @@
 // The lane keeps the same channels, so the values are the same. Loads of channels past E - 1 are made at channel 0 and not
 // used (no branch around a load); stores there are not made. The 16-byte kernels are compiled for that width; the others take
 // the width as a wave-uniform argument: one switch in front of a group's loads.
-#include "pointset_common.h"
+#include "fused_common.h"
 
 #pragma clang fp contract(off)  // every rounding below is written out; nothing is fused behind the text
 
@@ -45,9 +46,7 @@ constexpr int HD_BLOCK = 512;              // channels per block
 constexpr int HD_RESIDENT = 2;             // blocks whose weights a wave of the forward keeps in registers (no part of the definition)
 constexpr int HD_FWD_ROWS = 64;            // rows per workgroup of the forward on a large grid, HD_FWD_ROWS_FEW on a small one (likewise)
 constexpr int HD_FWD_ROWS_FEW = 16;
-constexpr int HD_FEW_WORKGROUPS = 512;     // below two workgroups per compute unit (likewise)
 constexpr int HD_AHEAD = 4;                // rows of x a wave has in flight (likewise)
-constexpr int HD_MERGE_AHEAD = 16;         // partials a thread of the merge has in flight (likewise)
 static_assert(HD_CHUNK == 128 && HD_CHUNK % HD_WAVES == 0 && HD_BLOCK == HD_LANE * 64, "the chunk and block shapes are part of the definition");
 static_assert(HD_FWD_ROWS % (HD_AHEAD * HD_WAVES) == 0 && HD_FWD_ROWS_FEW % (HD_AHEAD * HD_WAVES) == 0, "a workgroup's rows are whole groups");
 
@@ -333,32 +332,11 @@ __global__ __launch_bounds__(HD_T) void head_bwd_kernel(const T* __restrict__ x,
   }
 }
 
-// grid (ceil(C (E + 1) / 256), S): element n of a cloud's partial is gWs[s, n] for n < C E, gbs[s, n - C E] after that
-__global__ __launch_bounds__(HD_T) void head_merge_kernel(const float* __restrict__ ws, float* __restrict__ gWs, float* __restrict__ gbs, int chunks,
-                                                          int E, int C) {
-  const int n = blockIdx.x * HD_T + threadIdx.x, per = C * E + C;
-  if (n >= per) return;
-  const size_t s = blockIdx.y;
-  const bool is_w = n < C * E;
-  if (!(is_w ? gWs : gbs)) return;
-  const float* mine = ws + s * chunks * (size_t)per + n;
-  float total = 0.f;
-  for (int c0 = 0; c0 < chunks; c0 += HD_MERGE_AHEAD) {  // the loads of a group issued together, the additions in order
-    float v[HD_MERGE_AHEAD];
-#pragma unroll
-    for (int u = 0; u < HD_MERGE_AHEAD; ++u) v[u] = mine[(size_t)(c0 + u < chunks ? c0 + u : c0) * per];
-#pragma unroll
-    for (int u = 0; u < HD_MERGE_AHEAD; ++u) total = c0 + u < chunks ? total + v[u] : total;
-  }
-  if (is_w) gWs[s * (size_t)C * E + n] = total;
-  else gbs[s * (size_t)C + (n - C * E)] = total;
-}
-
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
 // the checks the two entries share after the null pointers, in the order include/nova_hip.h states: dtype, C, E, N, S
 static int hd_check(const char* who, int dtype, int S, int N, int C, int E) {
-  if (bad_dtype(dtype)) return set_error(NOVA_ERR_ARG, "%s: unknown dtype code %d (NOVA_F32, NOVA_BF16, NOVA_F16)", who, dtype);
+  NOVA_REQUIRE(!bad_dtype(dtype), NOVA_ERR_ARG, "%s: unknown dtype code %d (NOVA_F32, NOVA_BF16, NOVA_F16)", who, dtype);
   NOVA_REQUIRE(C >= 1 && C <= HD_MAX_C, NOVA_ERR_SHAPE, "%s: C %d outside 1 .. %d (NOVA_HEAD_MAX_OUT)", who, C, HD_MAX_C);
   NOVA_REQUIRE(E >= 1 && E <= HD_MAX_E, NOVA_ERR_SHAPE, "%s: E %d outside 1 .. %d (NOVA_HEAD_MAX_DIM)", who, E, HD_MAX_E);
   NOVA_REQUIRE(N >= 1 && N <= HD_MAX_N, NOVA_ERR_SHAPE, "%s: N %d outside 1 .. %d (NOVA_HEAD_MAX_POINTS)", who, N, HD_MAX_N);
@@ -372,25 +350,6 @@ static int hd_bytes(int dtype, int E, const void* a, const void* b = nullptr) {
   for (uintptr_t bytes = 16; bytes > es; bytes /= 2)
     if (bits % bytes == 0) return (int)bytes;
   return (int)es;
-}
-
-// f(integral_constant<int, C>) for the runtime C in 1 .. 8 (hd_check has passed)
-template <typename F> static void hd_dispatch_c(int C, F&& f) {
-  switch (C) {
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    case 3: f(std::integral_constant<int, 3>{}); break;
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    case 5: f(std::integral_constant<int, 5>{}); break;
-    case 6: f(std::integral_constant<int, 6>{}); break;
-    case 7: f(std::integral_constant<int, 7>{}); break;
-    default: f(std::integral_constant<int, 8>{}); break;
-  }
-}
-
-template <typename F> static void hd_dispatch_flag(bool on, F&& f) {
-  if (on) f(std::true_type{});
-  else f(std::false_type{});
 }
 
 }  // namespace nova
@@ -411,18 +370,17 @@ int nova_pointset_head(const void* x, int dtype, const float* W, const float* bi
   const void* ins[3] = {x, W, bias};
   const size_t nins[3] = {(size_t)S * N * E * esize(dtype), (size_t)C * E * 4, (size_t)C * 4};
   const char* names[3] = {"x", "W", "bias"};
-  for (int b = 0; b < 3; ++b)
-    NOVA_REQUIRE(!ranges_overlap(out, no, ins[b], nins[b]), NOVA_ERR_ARG, "%s: out overlaps the input %s", who, names[b]);
+  NOVA_TRY(check_no_overlap(who, out, no, "out", ins, nins, names, 3));
   // a small grid (a single cloud, say) leaves compute units idle: there a workgroup takes fewer rows. A row's result does
   // not depend on who computes the others.
-  const int rows_per_wg = ((N + HD_FWD_ROWS - 1) / HD_FWD_ROWS) * S < HD_FEW_WORKGROUPS ? HD_FWD_ROWS_FEW : HD_FWD_ROWS;
+  const int rows_per_wg = ((N + HD_FWD_ROWS - 1) / HD_FWD_ROWS) * S < FEW_WORKGROUPS ? HD_FWD_ROWS_FEW : HD_FWD_ROWS;
   const dim3 grid((N + rows_per_wg - 1) / rows_per_wg, S), block(HD_T);
   const int bytes = hd_bytes(dtype, E, x);
   dispatch_dtype(dtype, [&](auto t) {
     using T = decltype(t);
-    hd_dispatch_c(C, [&](auto c) {
-      hd_dispatch_flag(E <= HD_RESIDENT * HD_BLOCK, [&](auto resident) {
-        hd_dispatch_flag(bytes == 16, [&](auto wide) {
+    dispatch_count8(C, [&](auto c) {
+      dispatch_flag(E <= HD_RESIDENT * HD_BLOCK, [&](auto resident) {
+        dispatch_flag(bytes == 16, [&](auto wide) {
           hipLaunchKernelGGL((head_fwd_kernel<T, decltype(c)::value, decltype(resident)::value, decltype(wide)::value>), grid, block, 0, st, (const T*)x, W,
                              bias, out, N, E, rows_per_wg, bytes);
         });
@@ -452,29 +410,21 @@ int nova_pointset_head_bwd(const void* x, int dtype, const float* W, const float
   const void* outs[4] = {gx, gWs, gbs, gWs || gbs ? ws : nullptr};
   const size_t nouts[4] = {nx, (size_t)S * C * E * 4, (size_t)S * C * 4, (size_t)S * chunks * ((size_t)C * E + C) * 4};
   const char* onames[4] = {"gx", "gWs", "gbs", "ws"};
-  for (int a = 0; a < 4; ++a) {
-    for (int b = 0; b < 3; ++b)
-      NOVA_REQUIRE(!ranges_overlap(outs[a], nouts[a], ins[b], nins[b]), NOVA_ERR_ARG, "%s: %s overlaps the input %s", who, onames[a], names[b]);
-    for (int b = a + 1; b < 4; ++b)
-      NOVA_REQUIRE(!ranges_overlap(outs[a], nouts[a], outs[b], nouts[b]), NOVA_ERR_ARG, "%s: %s and %s overlap each other", who, onames[a], onames[b]);
-  }
-  // a small grid: the channel blocks are spread over grid.z, one per workgroup. A block's results do not depend on who
-  // computes the others.
-  const unsigned split = chunks * S < HD_FEW_WORKGROUPS ? (E + HD_BLOCK - 1) / HD_BLOCK : 1;
-  const dim3 grid(chunks, S, gx || gWs ? split : 1), block(HD_T);
+  NOVA_TRY(check_no_overlap(who, outs, nouts, onames, 4, ins, nins, names, 3));
+  const dim3 grid(chunks, S, gx || gWs ? few_workgroups_split(chunks * S, E, HD_BLOCK) : 1), block(HD_T);
   float* part = gWs || gbs ? ws : nullptr;
   const int bytes = hd_bytes(dtype, E, gWs ? x : nullptr, gx);
   dispatch_dtype(dtype, [&](auto t) {
     using T = decltype(t);
-    hd_dispatch_c(C, [&](auto c) {
-      hd_dispatch_flag(bytes == 16, [&](auto wide) {
+    dispatch_count8(C, [&](auto c) {
+      dispatch_flag(bytes == 16, [&](auto wide) {
         hipLaunchKernelGGL((head_bwd_kernel<T, decltype(c)::value, decltype(wide)::value>), grid, block, 0, st, (const T*)x, W, g, clamp, (T*)gx, part, N,
                            E, gWs ? 1 : 0, gbs ? 1 : 0, bytes);
       });
     });
     return 0;
   });
-  if (part) hipLaunchKernelGGL(head_merge_kernel, dim3((C * E + C + HD_T - 1) / HD_T, S), block, 0, st, part, gWs, gbs, chunks, E, C);
+  if (part) ordered_sum(st, part, gWs, gbs, S, chunks, C * E + C, C * E);
   return check_launch(who);
 }
 

@@ -18,11 +18,12 @@
 //   posenc_bwd_kernel       the forward's shape; three accumulators per lane (one per coordinate), wave_sum, then lanes 0 .. 2
 //                           store gx; the x t products of a wave's rows are accumulated in row order, the four waves merged
 //                           in wave order through LDS, the chunk's partial written to the caller's workspace.
-//   posenc_gs_merge_kernel  one thread per element of gs [S, 3]: the chunk partials in ascending chunk order.
+//   ordered_sum_kernel      (fused_common.h) one thread per element of gs [S, 3]: the chunk partials in ascending chunk order.
+//                           This file defines no summing kernel of its own.
 // No atomics. A cloud's results depend on (x[s], scale, div, base[s] or g[s], N, E) alone.
 // WIDE: rows start on 8 bytes (E even, 8-byte-aligned out, base, g), so a pair moves as one 8-byte access; otherwise as two
 // 4-byte ones. The values are the same.
-#include "pointset_common.h"
+#include "fused_common.h"
 
 #pragma clang fp contract(off)  // every rounding below is written out; nothing is fused behind the text
 
@@ -159,22 +160,13 @@ __global__ __launch_bounds__(PE_T) void posenc_bwd_kernel(const float* __restric
   }
 }
 
-__global__ __launch_bounds__(PE_T) void posenc_gs_merge_kernel(const float* __restrict__ ws, float* __restrict__ gs, int S, int chunks) {
-  const size_t e = (size_t)blockIdx.x * PE_T + threadIdx.x;  // (s, c)
-  if (e >= (size_t)S * 3) return;
-  const size_t s = e / 3, c = e % 3;
-  float total = 0.f;
-  for (int ch = 0; ch < chunks; ++ch) total = total + ws[(s * chunks + ch) * 3 + c];
-  gs[e] = total;
-}
-
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
 // the checks both entries share, in the order include/nova_hip.h states: E, N, S
 static int pe_check(const char* who, int S, int N, int E) {
-  if (E < 6 || E > PE_MAX_E) return set_error(NOVA_ERR_SHAPE, "%s: E %d outside 6 .. %d (NOVA_POSENC_MAX_DIM)", who, E, PE_MAX_E);
-  if (N < 1 || N > PE_MAX_N) return set_error(NOVA_ERR_SHAPE, "%s: N %d outside 1 .. %d (NOVA_POSENC_MAX_POINTS)", who, N, PE_MAX_N);
-  if (S > 65535) return set_error(NOVA_ERR_SHAPE, "%s: %d clouds exceed one launch (65535)", who, S);
+  NOVA_REQUIRE(E >= 6 && E <= PE_MAX_E, NOVA_ERR_SHAPE, "%s: E %d outside 6 .. %d (NOVA_POSENC_MAX_DIM)", who, E, PE_MAX_E);
+  NOVA_REQUIRE(N >= 1 && N <= PE_MAX_N, NOVA_ERR_SHAPE, "%s: N %d outside 1 .. %d (NOVA_POSENC_MAX_POINTS)", who, N, PE_MAX_N);
+  NOVA_REQUIRE(S <= 65535, NOVA_ERR_SHAPE, "%s: %d clouds exceed one launch (65535)", who, S);
   return 0;
 }
 
@@ -199,18 +191,16 @@ int nova_pointset_posenc(const float* x, const float* scale, const float* div, c
                          void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   const char* who = "pointset_posenc";
-  if (const int rc = pe_check(who, S, N, E)) return rc;
+  NOVA_TRY(pe_check(who, S, N, E));
   if (S <= 0) return 0;
   const int F = E / 6;
   const size_t nx = (size_t)S * N * 12, no = (size_t)S * N * E * 4;
   const void* ins[4] = {x, scale, div, base};
   const size_t nins[4] = {nx, 12, (size_t)F * 4, no};
   const char* names[4] = {"x", "scale", "div", "base"};
-  for (int b = 0; b < 3; ++b)  // base may be NULL
-    if (!ins[b]) return set_error(NOVA_ERR_ARG, "%s: null pointer %s", who, names[b]);
-  if (!out) return set_error(NOVA_ERR_ARG, "%s: null pointer out", who);
-  for (int b = 0; b < 4; ++b)
-    if (ranges_overlap(out, no, ins[b], nins[b])) return set_error(NOVA_ERR_ARG, "%s: out overlaps the input %s", who, names[b]);
+  for (int b = 0; b < 3; ++b) NOVA_REQUIRE(ins[b], NOVA_ERR_ARG, "%s: null pointer %s", who, names[b]);  // base may be NULL
+  NOVA_REQUIRE(out, NOVA_ERR_ARG, "%s: null pointer out", who);
+  NOVA_TRY(check_no_overlap(who, out, no, "out", ins, nins, names, 4));
   const dim3 grid((N + PE_CHUNK - 1) / PE_CHUNK, S), block(PE_T);
   const bool wide = E % 2 == 0 && pe_aligned8(out) && pe_aligned8(base);
   if (base && wide) hipLaunchKernelGGL((posenc_fwd_kernel<true, true>), grid, block, 0, st, x, scale, div, base, out, N, E, F);
@@ -224,30 +214,24 @@ int nova_pointset_posenc_bwd(const float* x, const float* scale, const float* di
                              int N, int E, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   const char* who = "pointset_posenc_bwd";
-  if (const int rc = pe_check(who, S, N, E)) return rc;
+  NOVA_TRY(pe_check(who, S, N, E));
   if (S <= 0) return 0;
   const int F = E / 6, chunks = (N + PE_CHUNK - 1) / PE_CHUNK;
   const size_t nx = (size_t)S * N * 12, ng = (size_t)S * N * E * 4;
   const void* ins[4] = {x, scale, div, g};
   const size_t nins[4] = {nx, 12, (size_t)F * 4, ng};
   const char* names[4] = {"x", "scale", "div", "g"};
-  for (int b = 0; b < 4; ++b)
-    if (!ins[b]) return set_error(NOVA_ERR_ARG, "%s: null pointer %s", who, names[b]);
-  if (!gx && !gs) return set_error(NOVA_ERR_ARG, "%s: no gradient wanted (gx and gs are both NULL)", who);
-  if (gs && !ws) return set_error(NOVA_ERR_ARG, "%s: gs needs the workspace ws", who);
+  for (int b = 0; b < 4; ++b) NOVA_REQUIRE(ins[b], NOVA_ERR_ARG, "%s: null pointer %s", who, names[b]);
+  NOVA_REQUIRE(gx || gs, NOVA_ERR_ARG, "%s: no gradient wanted (gx and gs are both NULL)", who);
+  NOVA_REQUIRE(ws || !gs, NOVA_ERR_ARG, "%s: gs needs the workspace ws", who);
   const void* outs[3] = {gx, gs, gs ? ws : nullptr};
   const size_t nouts[3] = {nx, (size_t)S * 12, (size_t)S * chunks * 12};
   const char* onames[3] = {"gx", "gs", "ws"};
-  for (int a = 0; a < 3; ++a) {
-    for (int b = 0; b < 4; ++b)
-      if (ranges_overlap(outs[a], nouts[a], ins[b], nins[b])) return set_error(NOVA_ERR_ARG, "%s: %s overlaps the input %s", who, onames[a], names[b]);
-    for (int b = a + 1; b < 3; ++b)
-      if (ranges_overlap(outs[a], nouts[a], outs[b], nouts[b])) return set_error(NOVA_ERR_ARG, "%s: %s and %s overlap each other", who, onames[a], onames[b]);
-  }
+  NOVA_TRY(check_no_overlap(who, outs, nouts, onames, 3, ins, nins, names, 4));
   const dim3 grid(chunks, S);
   if (E % 2 == 0 && pe_aligned8(g)) pe_bwd_launch<true>(grid, st, x, scale, div, g, gx, gs, ws, N, E, F);
   else pe_bwd_launch<false>(grid, st, x, scale, div, g, gx, gs, ws, N, E, F);
-  if (gs) hipLaunchKernelGGL(posenc_gs_merge_kernel, dim3((unsigned)(((size_t)S * 3 + PE_T - 1) / PE_T)), dim3(PE_T), 0, st, ws, gs, S, chunks);
+  if (gs) ordered_sum(st, ws, gs, nullptr, S, chunks, 3, 3);
   return check_launch(who);
 }
 

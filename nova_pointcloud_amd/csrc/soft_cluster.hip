@@ -18,14 +18,15 @@
 //   soft_cluster_bwd_kernel    the forward's shape; per centre the LDS holds c, out, g, u = 1 / (mass + 1e-8) and gm. gx is
 //                              local to the point (no reduction); the 3 K sums of gc take the forward's reduction, chunk
 //                              partials to the workspace; gx or gc not wanted: its arithmetic is compiled out.
-//   soft_cluster_gc_merge_kernel   one thread per element of gc [S, K, 3]: the chunk partials in ascending chunk order.
-//   soft_cluster_sum_clouds_kernel one thread per element of [K, 3]: gc[s] in ascending s, for the shared centres' gradient.
+//   ordered_sum_kernel         (fused_common.h) one thread per element of gc [S, K, 3]: the chunk partials in ascending chunk
+//                              order; and one thread per element of [K, 3]: gc[s] in ascending s, for the shared centres' gradient.
 // No atomics. A cloud's results depend on (x[s], c, N, K, scale) and, backward, (out[s], mass[s], g[s], gm[s]) alone.
 //
 // Cost per (point, centre): the distance 6 + 17 (correctly rounded square root), the weight 3 (v_exp_f32 at a quarter rate),
 // the product with r 1, four accumulations: about 35 issue slots forward, and 12 bytes of x per point, so the forward is
 // bound by instruction issue, not by memory, from K = 2 on.
 #include "interp_common.h"
+#include "fused_common.h"
 
 #pragma clang fp contract(off)  // every rounding below is written out; nothing is fused behind the text
 
@@ -241,26 +242,6 @@ __global__ __launch_bounds__(SC_T) void soft_cluster_bwd_kernel(const float* __r
   if (WANT_GC) chunk_reduce<3 * KR>(acc, red, ws + (s * chunks + chunk) * (size_t)(3 * K), 3 * K);
 }
 
-__global__ __launch_bounds__(SC_T) void soft_cluster_gc_merge_kernel(const float* __restrict__ ws, float* __restrict__ gc, int S, int K,
-                                                                     int chunks) {
-  const size_t e = (size_t)blockIdx.x * SC_T + threadIdx.x;  // (s, k, axis)
-  const size_t per = (size_t)K * 3;
-  if (e >= (size_t)S * per) return;
-  const size_t s = e / per, q = e % per;
-  float total = 0.f;
-  for (int ch = 0; ch < chunks; ++ch) total = total + ws[(s * chunks + ch) * per + q];
-  gc[e] = total;
-}
-
-__global__ __launch_bounds__(SC_T) void soft_cluster_sum_clouds_kernel(const float* __restrict__ gc, float* __restrict__ gcs, int S,
-                                                                       int per) {
-  const int q = blockIdx.x * SC_T + threadIdx.x;  // (k, axis)
-  if (q >= per) return;
-  float total = 0.f;
-  for (int s = 0; s < S; ++s) total = total + gc[(size_t)s * per + q];
-  gcs[q] = total;
-}
-
 // ---- host side -----------------------------------------------------------------------------------------------------------
 
 // the checks both entries share, in the order include/nova_hip.h states: N, K, S (shape), then scale (argument)
@@ -343,9 +324,7 @@ int nova_pointset_soft_cluster_bwd(const float* x, const float* c, const float* 
   if (K <= 8) sc_bwd_launch<8>(grid, st, x, c, out, mass, g, gm, gx, gc, ws, N, K, cstride, scale);
   else if (K <= 16) sc_bwd_launch<16>(grid, st, x, c, out, mass, g, gm, gx, gc, ws, N, K, cstride, scale);
   else sc_bwd_launch<32>(grid, st, x, c, out, mass, g, gm, gx, gc, ws, N, K, cstride, scale);
-  if (gc)
-    hipLaunchKernelGGL(soft_cluster_gc_merge_kernel, dim3((unsigned)(((size_t)S * K * 3 + SC_T - 1) / SC_T)), dim3(SC_T), 0, st, ws, gc, S, K,
-                       chunks);
+  if (gc) ordered_sum(st, ws, gc, nullptr, S, chunks, 3 * K, 3 * K);
   return check_launch(who);
 }
 
@@ -356,7 +335,7 @@ int nova_pointset_soft_cluster_sum_clouds(const float* gc, float* gcs, int S, in
   if (S <= 0) return 0;
   if (!gc || !gcs) return set_error(NOVA_ERR_ARG, "%s: null pointer", who);
   if (ranges_overlap(gcs, (size_t)K * 12, gc, (size_t)S * K * 12)) return set_error(NOVA_ERR_ARG, "%s: gcs overlaps gc", who);
-  hipLaunchKernelGGL(soft_cluster_sum_clouds_kernel, dim3((K * 3 + SC_T - 1) / SC_T), dim3(SC_T), 0, st, gc, gcs, S, K * 3);
+  ordered_sum(st, gc, gcs, nullptr, 1, S, 3 * K, 3 * K);
   return check_launch(who);
 }
 

@@ -21,6 +21,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import hip
+from ._pointset import _all_floating, _all_tensors, _chunks, _on_gpu, _same_device, _sum_over
 
 DROPOUT_MAX_DIM = 16384  # == NOVA_DROPOUT_MAX_DIM of include/nova_hip.h
 DROPOUT_MAX_ROWS = 1 << 30  # == NOVA_DROPOUT_MAX_ROWS
@@ -63,12 +64,8 @@ def _dropout_arguments(x, bias, residual, p, activation, seed, subsequence, gene
     """ValueError for everything about the arguments that does not need the GPU (so it holds for CPU tensors too), in one
     order: types, dtypes, shapes, D range, devices, p, activation (and activation with residual), seed / subsequence range."""
     given = [(x, "x")] + [(t, name) for t, name in ((bias, "bias"), (residual, "residual")) if t is not None]
-    for t, name in given:
-        if not torch.is_tensor(t):
-            raise ValueError(f"{name}: expected a tensor, got {type(t).__name__}")
-    for t, name in given:
-        if not t.is_floating_point():
-            raise ValueError(f"{name}: expected a floating dtype, got {t.dtype}")
+    _all_tensors(given)
+    _all_floating(given)
     if residual is not None and residual.dtype != x.dtype:
         raise ValueError(f"residual: expected x's dtype {x.dtype}, got {residual.dtype}")
     if x.dim() < 1:
@@ -82,9 +79,7 @@ def _dropout_arguments(x, bias, residual, p, activation, seed, subsequence, gene
         raise ValueError(f"x: the dropout kernel takes 1 .. {DROPOUT_MAX_DIM} columns, got {D}")
     if x.numel() // D > DROPOUT_MAX_ROWS:
         raise ValueError(f"x: the dropout kernel takes at most {DROPOUT_MAX_ROWS} rows, got {x.numel() // D}")
-    for t, name in given[1:]:
-        if t.device != x.device:
-            raise ValueError(f"x and {name} must be on the same device, got {x.device} and {t.device}")
+    _same_device(given)
     if isinstance(p, bool) or not isinstance(p, numbers.Real) or not 0 <= p <= 1:  # a NaN fails the comparison
         raise ValueError(f"p must be a real number in [0, 1], got {p!r}")
     if activation not in _ACTIVATIONS:
@@ -131,21 +126,18 @@ class _BiasDropoutAdd(torch.autograd.Function):
             gc = g.contiguous()
             D = g.shape[-1]
             rows = g.numel() // D
-            chunks = (rows + DROPOUT_CHUNK - 1) // DROPOUT_CHUNK
+            chunks = _chunks(rows, DROPOUT_CHUNK)
             gx = torch.empty_like(gc) if want_x else None  # in the tensor's own dtype, rounded once by the kernel
-            # no row launches nothing, so nothing writes the sum over the chunks: it starts from +0 and stays there
-            gb = (torch.empty if rows > 0 else torch.zeros)(D, dtype=torch.float32, device=g.device) if want_b else None
-            if rows > 0:
-                parts = torch.empty(chunks, D, dtype=torch.float32, device=g.device) if want_b else None
-                with torch.cuda.device(g.device):
-                    stream = hip.stream_ptr()
+            parts = torch.empty(chunks, D, dtype=torch.float32, device=g.device) if want_b else None
+            with torch.cuda.device(g.device):
+                stream = hip.stream_ptr()
+                if rows > 0:
                     hip.call("nova_bias_dropout_add_bwd", gc.data_ptr(), out.data_ptr() if out is not None else None, hip.dtype_code(gc.dtype),
                              gx.data_ptr() if want_x else None, parts.data_ptr() if want_b else None, rows, D, 0, T, scale, seed, subsequence, act,
                              stream)
                     stats["backward_launches"] += 1
-                    if want_b:  # the chunk rows in ascending order
-                        hip.call("nova_pointset_embed_sum_clouds", parts.data_ptr(), gb.data_ptr(), chunks, D, stream)
-                        stats["bias_sum_launches"] += 1
+                if want_b:  # the chunk rows in ascending order; no row: nothing is launched and the sum is +0
+                    gb = _sum_over("nova_pointset_embed_sum_clouds", parts, chunks, (D,), D, stream=stream, stats=stats, key="bias_sum_launches")
         return gx, gb, g if want_r else None, None, None, None, None, None
 
 
@@ -174,9 +166,7 @@ def bias_dropout_add(x, bias=None, residual=None, p=0.1, training=True, activati
     ValueError, in this order: types, dtypes, shapes, D range, devices, p, activation (and activation with residual),
     seed / subsequence range. NovaHipError for CPU tensors."""
     _dropout_arguments(x, bias, residual, p, activation, seed, subsequence, generator)
-    for t, name in ((x, "x"), (bias, "bias"), (residual, "residual")):
-        if t is not None and not t.is_cuda:
-            raise hip.NovaHipError(f"{name}: the fused dropout runs on the GPU (got a CPU tensor)")
+    _on_gpu(((x, "x"), (bias, "bias"), (residual, "residual")), "the fused dropout")
     T, scale, seed = mask_numbers(p, training, seed, generator)
     native = lambda t: (t if t.dtype in _NATIVE else t.float()).contiguous() if t is not None else None
     return _BiasDropoutAdd.apply(native(x), bias.float().contiguous() if bias is not None else None, native(residual), T, scale, seed, subsequence,

@@ -15,12 +15,12 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import hip
-from ._pointset import _at, _clouds_per_launch, _launches, _launching
+from ._pointset import (MAX_CLOUDS_PER_CALL, _all_floating, _all_tensors, _allocator, _at, _budget_clouds_per_launch, _chunks, _clouds_per_launch,
+                        _launch_stream, _launching, _on_gpu, _same_device, _sum_over)
 
 POSENC_MAX_DIM = 4096  # == NOVA_POSENC_MAX_DIM of include/nova_hip.h
 POSENC_MAX_POINTS = 65536  # == NOVA_POSENC_MAX_POINTS
 POSENC_CHUNK = 32  # == NOVA_POSENC_CHUNK: rows per workgroup, the unit of the backward's workspace
-_MAX_CLOUDS_PER_CALL = 65535  # clouds go in grid.y
 # Per-launch budget, ESTIMATED BY COUNT, not from a measured time: (sin, cos) pairs a launch forms, each one IEEE division
 # and one accurate sincosf (about 80 issue slots) and 8 bytes stored (forward) or read (backward); 2^28 pairs are 2 GiB of
 # output, under a millisecond of stores and about as much arithmetic on 256 compute units.
@@ -47,26 +47,14 @@ def _reference_table(embed_dim, device):
     return _tables[key]
 
 
-def _default_clouds_per_launch(N, E):
-    return max(1, min(_POSENC_PAIRS_PER_LAUNCH // (N * 3 * (E // 6)), _MAX_CLOUDS_PER_CALL))
-
-
-def _chunks(N):
-    return (N + POSENC_CHUNK - 1) // POSENC_CHUNK
-
-
 def _encoding_arguments(points, scale, embed_dim, base, div_term):
     """ValueError for everything about the arguments that does not need the GPU (so it holds for CPU tensors too), in one
     order: types, dtypes, shapes, cloud counts, ranges, devices."""
     given = [(points, "points"), (scale, "scale")] + [(t, name) for t, name in ((base, "base"), (div_term, "div_term")) if t is not None]
-    for t, name in given:
-        if not torch.is_tensor(t):
-            raise ValueError(f"{name}: expected a tensor, got {type(t).__name__}")
+    _all_tensors(given)
     if not isinstance(embed_dim, int) or isinstance(embed_dim, bool):
         raise ValueError(f"embed_dim must be an integer, got {embed_dim!r}")
-    for t, name in given:
-        if not t.is_floating_point():
-            raise ValueError(f"{name}: expected a floating dtype, got {t.dtype}")
+    _all_floating(given)
     if points.dim() != 3 or points.shape[-1] != 3:
         raise ValueError(f"points: expected [S, N, 3] clouds, got {tuple(points.shape)}")
     if tuple(scale.shape) != (3,):
@@ -85,9 +73,7 @@ def _encoding_arguments(points, scale, embed_dim, base, div_term):
         used = div_term[:embed_dim // 6]
         if not bool(((used > 0) & torch.isfinite(used)).all()):
             raise ValueError("div_term: the divisors must be positive and finite")
-    for t, name in given[1:]:
-        if t.device != points.device:
-            raise ValueError(f"points and {name} must be on the same device, got {points.device} and {t.device}")
+    _same_device(given)
 
 
 class _Encoding(torch.autograd.Function):
@@ -116,23 +102,19 @@ class _Encoding(torch.autograd.Function):
         if not (want_x or want_s):
             return None, None, None, gb, None, None
         g = g.float().contiguous()
-        gx = torch.empty_like(x) if want_x else None
-        gs = torch.empty(S, 3, dtype=torch.float32, device=x.device) if want_s else None  # per cloud
-        ws = torch.empty(min(S, per) * _chunks(N) * 3, dtype=torch.float32, device=x.device) if want_s else None
-        # written out, not _launching: the sum over the clouds follows the loop on the same device and stream
-        with torch.cuda.device(x.device):
-            stream = hip.stream_ptr()
-            for s0, count in _launches(S, per):
+        new = _allocator(S, x.device)
+        gx = new(S, N, 3) if want_x else None
+        gs = new(S, 3) if want_s else None  # per cloud
+        ws = new(min(S, per) * _chunks(N, POSENC_CHUNK) * 3) if want_s else None
+        with _launch_stream(x.device, S, per) as (stream, spans):
+            for s0, count in spans:
                 hip.call("nova_pointset_posenc_bwd", _at(x, s0), scale.data_ptr(), div.data_ptr(), _at(g, s0), _at(gx, s0), _at(gs, s0),
                          ws.data_ptr() if want_s else None, count, N, E, stream)
                 stats["point_grad_launches"] += 1 if want_x else 0
                 stats["scale_grad_launches"] += 1 if want_s else 0
             if want_s:  # after every launch has written its clouds: ascending cloud order, whatever the split
-                gsum = torch.zeros(3, dtype=torch.float32, device=x.device)
-                if S > 0:  # the cloud sum of the soft cluster pooling with K = 1: the same contract (include/nova_hip.h)
-                    hip.call("nova_pointset_soft_cluster_sum_clouds", gs.data_ptr(), gsum.data_ptr(), S, 1, stream)
-                    stats["cloud_sum_launches"] += 1
-                gs = gsum
+                # the cloud sum of the soft cluster pooling with K = 1: the same contract (include/nova_hip.h)
+                gs = _sum_over("nova_pointset_soft_cluster_sum_clouds", gs, S, (3,), 1, stream=stream, stats=stats, key="cloud_sum_launches")
         return gx, gs, None, gb, None, None
 
 
@@ -159,10 +141,9 @@ def coordinate_encoding(points, scale, embed_dim, base=None, div_term=None, max_
     ValueError, in this order: types, dtypes, shapes, cloud counts, ranges (embed_dim, points per cloud, the table's
     values), devices, max_clouds_per_launch. NovaHipError for CPU tensors."""
     _encoding_arguments(points, scale, embed_dim, base, div_term)
-    per = _clouds_per_launch(max_clouds_per_launch, _default_clouds_per_launch(points.shape[1], embed_dim), _MAX_CLOUDS_PER_CALL)
-    for t, name in ((points, "points"), (scale, "scale"), (base, "base"), (div_term, "div_term")):
-        if t is not None and not t.is_cuda:
-            raise hip.NovaHipError(f"{name}: the coordinate encoding runs on the GPU (got a CPU tensor)")
+    per = _clouds_per_launch(max_clouds_per_launch, _budget_clouds_per_launch(_POSENC_PAIRS_PER_LAUNCH, points.shape[1] * 3 * (embed_dim // 6)),
+                             MAX_CLOUDS_PER_CALL)
+    _on_gpu(((points, "points"), (scale, "scale"), (base, "base"), (div_term, "div_term")), "the coordinate encoding")
     div = _reference_table(embed_dim, points.device) if div_term is None else div_term.detach().float().contiguous()
     xs = points.float().contiguous()
     sc = scale.float().contiguous()

@@ -19,13 +19,13 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import hip
-from ._pointset import _at, _clouds_per_launch, _launches, _launching
+from ._pointset import (MAX_CLOUDS_PER_CALL, _all_floating, _all_tensors, _allocator, _at, _budget_clouds_per_launch, _chunks, _clouds_per_launch,
+                        _launch_stream, _launching, _on_gpu, _same_device, _sum_over)
 
 EMBED_MAX_IN = 8  # == NOVA_EMBED_MAX_IN of include/nova_hip.h
 EMBED_MAX_DIM = 4096  # == NOVA_EMBED_MAX_DIM
 EMBED_MAX_POINTS = 65536  # == NOVA_EMBED_MAX_POINTS
 EMBED_CHUNK = 128  # == NOVA_EMBED_CHUNK: rows per workgroup of the backward, the unit of its workspace
-_MAX_CLOUDS_PER_CALL = 65535  # clouds go in grid.y
 # Per-launch budget, ESTIMATED BY BYTES, not from a measured time: the output (forward) or the incoming gradient (backward)
 # of a launch, 4 N E bytes per cloud. 2 GiB move in about a third of a millisecond at the 6.3e12 B/s a streaming kernel
 # reaches on this chip, long against the launch overhead and short enough to leave the queue responsive.
@@ -38,25 +38,13 @@ _EMBED_BYTES_PER_LAUNCH = 1 << 31
 stats = {"forward_launches": 0, "backward_launches": 0, "pos_grad_launches": 0, "cloud_sum_launches": 0}
 
 
-def _default_clouds_per_launch(N, E):
-    return max(1, min(_EMBED_BYTES_PER_LAUNCH // (4 * N * E), _MAX_CLOUDS_PER_CALL))
-
-
-def _chunks(N):
-    return (N + EMBED_CHUNK - 1) // EMBED_CHUNK
-
-
 def _embed_arguments(points, weight, bias, pos, cond, base):
     """ValueError for everything about the arguments that does not need the GPU (so it holds for CPU tensors too), in one
     order: types, dtypes, shapes, cloud counts, ranges, devices."""
     given = [(points, "points"), (weight, "weight")] + [(t, name) for t, name in ((bias, "bias"), (pos, "pos"), (cond, "cond"), (base, "base"))
                                                         if t is not None]
-    for t, name in given:
-        if not torch.is_tensor(t):
-            raise ValueError(f"{name}: expected a tensor, got {type(t).__name__}")
-    for t, name in given:
-        if not t.is_floating_point():
-            raise ValueError(f"{name}: expected a floating dtype, got {t.dtype}")
+    _all_tensors(given)
+    _all_floating(given)
     if points.dim() != 3:
         raise ValueError(f"points: expected [S, N, C] clouds, got {tuple(points.shape)}")
     S, N, C = points.shape
@@ -82,9 +70,7 @@ def _embed_arguments(points, weight, bias, pos, cond, base):
         raise ValueError(f"weight: the embedding kernel takes 1 .. {EMBED_MAX_DIM} channels, got {E}")
     if not 1 <= N <= EMBED_MAX_POINTS:
         raise ValueError(f"points: the embedding kernel takes 1 .. {EMBED_MAX_POINTS} points per cloud, got {N}")
-    for t, name in given[1:]:
-        if t.device != points.device:
-            raise ValueError(f"points and {name} must be on the same device, got {points.device} and {t.device}")
+    _same_device(given)
 
 
 class _PointEmbed(torch.autograd.Function):
@@ -117,18 +103,15 @@ class _PointEmbed(torch.autograd.Function):
         if not (want_x or want_w or want_b or want_p or want_c):
             return None, None, None, None, None, gbase, None
         g = g.float().contiguous()
-        # an empty cloud set launches nothing, so nothing writes the sums over the clouds: they start from +0 and stay there
-        new = lambda *shape: (torch.empty if S > 0 else torch.zeros)(*shape, dtype=torch.float32, device=x.device)
+        new = _allocator(S, x.device)
         gx = new(S, N, C) if want_x else None
         gWs = new(S, E, C) if want_w else None  # per cloud
         gcs = new(S, E) if want_b or want_c else None  # per cloud: cond's gradient as it stands
-        ws = new(min(S, per) * _chunks(N) * E * (C + 1)) if want_w or want_b or want_c else None
+        ws = new(min(S, per) * _chunks(N, EMBED_CHUNK) * E * (C + 1)) if want_w or want_b or want_c else None
         gpos = new(N, E) if want_p else None
         gW = gb = None
-        # written out, not _launching: the sums over the clouds follow the loop on the same device and stream
-        with torch.cuda.device(x.device):
-            stream = hip.stream_ptr()
-            for n, (s0, count) in enumerate(_launches(S, per)):
+        with _launch_stream(x.device, S, per) as (stream, spans):
+            for n, (s0, count) in enumerate(spans):
                 if gx is not None or ws is not None:
                     hip.call("nova_pointset_embed_bwd", _at(x, s0), W.data_ptr(), _at(g, s0), _at(gx, s0), _at(gWs, s0), _at(gcs, s0),
                              ws.data_ptr() if ws is not None else None, count, N, C, E, stream)
@@ -138,15 +121,9 @@ class _PointEmbed(torch.autograd.Function):
                     stats["pos_grad_launches"] += 1
             # after every launch has written its clouds: ascending cloud order, whatever the split
             if want_w:
-                gW = new(E, C)
-                if S > 0:
-                    hip.call("nova_pointset_embed_sum_clouds", gWs.data_ptr(), gW.data_ptr(), S, E * C, stream)
-                    stats["cloud_sum_launches"] += 1
+                gW = _sum_over("nova_pointset_embed_sum_clouds", gWs, S, (E, C), E * C, stream=stream, stats=stats, key="cloud_sum_launches")
             if want_b:
-                gb = new(E)
-                if S > 0:
-                    hip.call("nova_pointset_embed_sum_clouds", gcs.data_ptr(), gb.data_ptr(), S, E, stream)
-                    stats["cloud_sum_launches"] += 1
+                gb = _sum_over("nova_pointset_embed_sum_clouds", gcs, S, (E,), E, stream=stream, stats=stats, key="cloud_sum_launches")
         return gx, gW, gb, gpos, gcs if want_c else None, gbase, None
 
 
@@ -174,10 +151,8 @@ def point_embed(points, weight, bias=None, pos=None, cond=None, base=None, max_c
     devices, max_clouds_per_launch. NovaHipError for CPU tensors."""
     _embed_arguments(points, weight, bias, pos, cond, base)
     N, E = points.shape[1], weight.shape[0]
-    per = _clouds_per_launch(max_clouds_per_launch, _default_clouds_per_launch(N, E), _MAX_CLOUDS_PER_CALL)
-    for t, name in ((points, "points"), (weight, "weight"), (bias, "bias"), (pos, "pos"), (cond, "cond"), (base, "base")):
-        if t is not None and not t.is_cuda:
-            raise hip.NovaHipError(f"{name}: the point embedding runs on the GPU (got a CPU tensor)")
+    per = _clouds_per_launch(max_clouds_per_launch, _budget_clouds_per_launch(_EMBED_BYTES_PER_LAUNCH, 4 * N * E), MAX_CLOUDS_PER_CALL)
+    _on_gpu(((points, "points"), (weight, "weight"), (bias, "bias"), (pos, "pos"), (cond, "cond"), (base, "base")), "the point embedding")
     f32 = lambda t: t.float().contiguous() if t is not None else None
     table = None
     if pos is not None:

@@ -14,19 +14,17 @@ nova_pointset_head.
 GPU tensors only for the kernels: NovaHipError for CPU tensors or a missing library. Results are bitwise reproducible: the
 same for every launch split, every position in the batch and every run, forward and backward (the per-cloud gradients
 are summed in ascending cloud order by a kernel, after every launch)."""
-import math
-
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import hip
-from ._pointset import _at, _clouds_per_launch, _launches, _launching
+from ._pointset import (MAX_CLOUDS_PER_CALL, _all_floating, _all_tensors, _allocator, _at, _budget_clouds_per_launch, _check_clamp, _chunks,
+                        _clouds_per_launch, _launch_stream, _launching, _on_gpu, _same_device, _sum_over)
 
 HEAD_MAX_OUT = 8  # == NOVA_HEAD_MAX_OUT of include/nova_hip.h
 HEAD_MAX_DIM = 4096  # == NOVA_HEAD_MAX_DIM
 HEAD_MAX_POINTS = 65536  # == NOVA_HEAD_MAX_POINTS
 HEAD_CHUNK = 128  # == NOVA_HEAD_CHUNK: rows per workgroup of the backward, the unit of its workspace
-_MAX_CLOUDS_PER_CALL = 65535  # clouds go in grid.y
 _NATIVE = (torch.float32, torch.bfloat16, torch.float16)  # what the kernels read and write as it is
 # Per-launch budget, ESTIMATED BY BYTES as in point_embed.py, not from a measured time: the rows of x of a launch (the
 # forward's read; the backward moves twice that), N E elements of x's own size per cloud. 2 GiB move in about a third of a
@@ -39,24 +37,12 @@ _HEAD_BYTES_PER_LAUNCH = 1 << 31
 stats = {"forward_launches": 0, "backward_launches": 0, "cloud_sum_launches": 0}
 
 
-def _default_clouds_per_launch(N, E, itemsize):
-    return max(1, min(_HEAD_BYTES_PER_LAUNCH // (itemsize * N * E), _MAX_CLOUDS_PER_CALL))
-
-
-def _chunks(N):
-    return (N + HEAD_CHUNK - 1) // HEAD_CHUNK
-
-
 def _head_arguments(x, weight, bias, grad_clamp):
     """ValueError for everything about the arguments that does not need the GPU (so it holds for CPU tensors too), in one
     order: types, dtypes, shapes, ranges, devices, grad_clamp."""
     given = [(x, "x"), (weight, "weight")] + ([(bias, "bias")] if bias is not None else [])
-    for t, name in given:
-        if not torch.is_tensor(t):
-            raise ValueError(f"{name}: expected a tensor, got {type(t).__name__}")
-    for t, name in given:
-        if not t.is_floating_point():
-            raise ValueError(f"{name}: expected a floating dtype, got {t.dtype}")
+    _all_tensors(given)
+    _all_floating(given)
     if x.dim() != 3:
         raise ValueError(f"x: expected [S, N, E] rows, got {tuple(x.shape)}")
     S, N, E = x.shape
@@ -71,11 +57,8 @@ def _head_arguments(x, weight, bias, grad_clamp):
         raise ValueError(f"x: the head kernel takes 1 .. {HEAD_MAX_DIM} channels, got {E}")
     if not 1 <= N <= HEAD_MAX_POINTS:
         raise ValueError(f"x: the head kernel takes 1 .. {HEAD_MAX_POINTS} points per cloud, got {N}")
-    for t, name in given[1:]:
-        if t.device != x.device:
-            raise ValueError(f"x and {name} must be on the same device, got {x.device} and {t.device}")
-    if grad_clamp is not None and not (isinstance(grad_clamp, (int, float)) and not isinstance(grad_clamp, bool) and 0 < grad_clamp < math.inf):
-        raise ValueError(f"grad_clamp must be None or a positive finite number, got {grad_clamp!r}")
+    _same_device(given)
+    _check_clamp(grad_clamp, "grad_clamp")
 
 
 class _PointHead(torch.autograd.Function):
@@ -105,32 +88,23 @@ class _PointHead(torch.autograd.Function):
         if g is None or not (want_x or want_w or want_b):
             return (None,) * 5
         g = g.float().contiguous()
-        # an empty cloud set launches nothing, so nothing writes the sums over the clouds: they start from +0 and stay there
-        new = lambda *shape, dtype=torch.float32: (torch.empty if S > 0 else torch.zeros)(*shape, dtype=dtype, device=x.device)
+        new = _allocator(S, x.device)
         gx = new(S, N, E, dtype=x.dtype) if want_x else None  # in x's own dtype, rounded once by the kernel
         gWs = new(S, C, E) if want_w else None  # per cloud
         gbs = new(S, C) if want_b else None
-        ws = new(min(S, per) * _chunks(N) * C * (E + 1)) if want_w or want_b else None
+        ws = new(min(S, per) * _chunks(N, HEAD_CHUNK) * C * (E + 1)) if want_w or want_b else None
         gW = gb = None
         code = hip.dtype_code(x.dtype)
-        # written out, not _launching: the sums over the clouds follow the loop on the same device and stream
-        with torch.cuda.device(x.device):
-            stream = hip.stream_ptr()
-            for s0, count in _launches(S, per):
+        with _launch_stream(x.device, S, per) as (stream, spans):
+            for s0, count in spans:
                 hip.call("nova_pointset_head_bwd", _at(x, s0) if want_w else None, code, W.data_ptr(), _at(g, s0), ctx.clamp, _at(gx, s0), _at(gWs, s0),
                          _at(gbs, s0), ws.data_ptr() if ws is not None else None, count, N, C, E, stream)
                 stats["backward_launches"] += 1
             # after every launch has written its clouds: ascending cloud order, whatever the split
             if want_w:
-                gW = new(C, E)
-                if S > 0:
-                    hip.call("nova_pointset_embed_sum_clouds", gWs.data_ptr(), gW.data_ptr(), S, C * E, stream)
-                    stats["cloud_sum_launches"] += 1
+                gW = _sum_over("nova_pointset_embed_sum_clouds", gWs, S, (C, E), C * E, stream=stream, stats=stats, key="cloud_sum_launches")
             if want_b:
-                gb = new(C)
-                if S > 0:
-                    hip.call("nova_pointset_embed_sum_clouds", gbs.data_ptr(), gb.data_ptr(), S, C, stream)
-                    stats["cloud_sum_launches"] += 1
+                gb = _sum_over("nova_pointset_embed_sum_clouds", gbs, S, (C,), C, stream=stream, stats=stats, key="cloud_sum_launches")
         return gx, gW, gb, None, None
 
 
@@ -158,10 +132,8 @@ def point_head(x, weight, bias=None, grad_clamp=None, max_clouds_per_launch=None
     _head_arguments(x, weight, bias, grad_clamp)
     N, E = x.shape[1], x.shape[2]
     itemsize = x.element_size() if x.dtype in _NATIVE else 4
-    per = _clouds_per_launch(max_clouds_per_launch, _default_clouds_per_launch(N, E, itemsize), _MAX_CLOUDS_PER_CALL)
-    for t, name in ((x, "x"), (weight, "weight"), (bias, "bias")):
-        if t is not None and not t.is_cuda:
-            raise hip.NovaHipError(f"{name}: the point head runs on the GPU (got a CPU tensor)")
+    per = _clouds_per_launch(max_clouds_per_launch, _budget_clouds_per_launch(_HEAD_BYTES_PER_LAUNCH, itemsize * N * E), MAX_CLOUDS_PER_CALL)
+    _on_gpu(((x, "x"), (weight, "weight"), (bias, "bias")), "the point head")
     f32 = lambda t: t.float().contiguous() if t is not None else None
     rows = (x if x.dtype in _NATIVE else x.float()).contiguous()
     return _PointHead.apply(rows, f32(weight), f32(bias), float(grad_clamp) if grad_clamp is not None else 0.0, per)

@@ -345,7 +345,10 @@ def test_header_constants_and_kernel_shape():
     assert "#pragma clang fp contract(off)" in source
     for name in names:  # the file defines its own entry points, with their checks
         assert re.search(r"\bint " + name + r"\(", source), name
-    assert "embed_sum_clouds_kernel" not in source  # the sum over the clouds is point_embed.hip's, not a second copy
+    # the file defines no summing kernel of its own: the chunk merge is fused_common.h's ordered_sum_kernel, and the sum over
+    # the clouds is point_embed.hip's entry point, called from Python
+    assert re.findall(r"void (\w+_kernel)\(", source) == ["head_fwd_kernel", "head_bwd_kernel"]
+    assert '#include "fused_common.h"' in source and "ordered_sum(st, part, gWs, gbs," in source and "sum_clouds" not in source
     capi = open(os.path.join(ROOT, "nova_pointcloud_amd", "csrc", "capi.hip")).read()
     assert "pointset_head" not in capi
     code = re.sub(r"//.*", "", source)

@@ -319,7 +319,10 @@ def test_header_constants_and_kernel_shape():
     assert "#pragma clang fp contract(off)" in source
     code = re.sub(r"//.*", "", source)
     assert "atomic" not in code.lower() and "__sinf" not in code and "__cosf" not in code and "__sincosf" not in code
-    assert code.count("sum_clouds") == 0  # the cloud sum is the soft cluster pooling's kernel, called from Python
+    # the file defines no summing kernel of its own: the chunk merge is fused_common.h's ordered_sum_kernel, and the cloud sum
+    # is the soft cluster pooling's entry point, called from Python
+    assert re.findall(r"void (\w+_kernel)\(", code) == ["posenc_fwd_kernel", "posenc_bwd_kernel"]
+    assert '#include "fused_common.h"' in code and "ordered_sum(st, ws, gs," in code and code.count("sum_clouds") == 0
     makefile = open(os.path.join(ROOT, "nova_pointcloud_amd", "csrc", "Makefile")).read()
     assert "posenc.hip" in re.search(r"^SRCS := (.*)$", makefile, flags=re.M).group(1).split()
     assert "fast-math" not in makefile and "ffast" not in makefile
