@@ -930,6 +930,81 @@ int nova_bias_dropout_add_bwd(const void* g, const void* out, int dtype, void* g
                               long long first_row, unsigned long long T, float scale, unsigned long long seed,
                               unsigned long long subsequence, int act, void* stream);
 
+/* Fused AdamW step with in-kernel gradient clipping over a LIST of tensors: what the reference's trainer does after the
+ * backward, torch.nn.utils.clip_grad_norm_ and then torch.optim.AdamW with betas (0.9, 0.999) (train_newloss.py:827-841 and
+ * :1060-1082). In torch that is a norm pass, a read-modify-write of every gradient and about a dozen elementwise passes over
+ * every parameter. Here each gradient is read twice (once for the norm, once for the update) and never written, each
+ * parameter and each moment is read and written once, and the host never waits for the device.
+ * nova_adamw_tensor: one tensor of the list. param and grad are n contiguous elements of the nova_dtype `dtype` (NOVA_F32,
+ *   NOVA_BF16, NOVA_F16); exp_avg and exp_avg_sq are float32 [n]; master is float32 [n], the full-precision copy of a 16-bit
+ *   (or any) parameter, or NULL. The seven numbers are float32 values the HOST forms in float64 and rounds once each, from the
+ *   group's lr, (beta1, beta2), eps, weight_decay and the tensor's step count t >= 1 (the caller's business):
+ *     decay = 1 - lr * weight_decay     w1 = 1 - beta1     b2 = beta2     w2 = 1 - beta2
+ *     q = sqrt(1 - beta2^t)             a = lr / (1 - beta1^t)            eps
+ * nova_adamw_sumsq: the float32 sum of the squares of every gradient element of the list (only grad, n and dtype are read).
+ *   Tensor i is cut into ceil(n_i / NOVA_ADAMW_CHUNK) chunks of NOVA_ADAMW_CHUNK = 8192 elements, the last one short; the
+ *   chunks of the whole list, in list order and ascending inside a tensor, are numbered 0 .. P - 1 (a tensor with n = 0 has
+ *   none). The partial of a chunk that starts at element c0:
+ *     thread t = 0 .. 255 owns the units u = t, 256 + t, 512 + t, 768 + t of the chunk, unit u being the 8 elements
+ *     c0 + 8 u .. c0 + 8 u + 7. From acc = +0, over its units in that order and the elements of a unit in ascending order:
+ *     x = float32(grad[e]) (exact), acc = acc + x * x (the product rounded, then the sum). An element past n - 1 is not added.
+ *     Then the tree over the 256 values s[t] = acc: for h = 128, 64, .. 1: s[t] = s[t] + s[t + h] for every t < h. The
+ *     partial is s[0].
+ *   workspace[k] = the partial of chunk k (plain stores: float32 [workspace_floats], workspace_floats >= P). The total:
+ *     the partials as rows of NOVA_ADAMW_SUM_COLUMNS = 256: column n = 0 .. 255 is the sum, from +0 in ascending k, of
+ *     workspace[256 k + n] over the k with 256 k + n < P (total = total + v every time); then the same tree over the 256
+ *     columns. *sumsq = s[0], and *norm = sqrt(*sumsq), correctly rounded, when norm is not NULL (the total 2-norm of the
+ *     gradients before clipping, for the caller's log, from the same launch). (The order of ordered_sum with per = 256, whose last step is the tree, in one launch and with
+ *     no padding of the last row; one serial thread over about 10^5 partials would be a visible share of the call.)
+ *   The total stays on the device. P == 0 (an empty list, or only tensors with n = 0) launches nothing and leaves *sumsq and
+ *   *norm alone.
+ * nova_adamw_step: the update of every element of every tensor, one pass. sumsq is the device float32 of nova_adamw_sumsq or
+ *   NULL for "no clipping". Every operation is float32, rounded once, nothing fused; sqrt and / are the correctly rounded ones:
+ *     s  = sumsq ? c > 1 ? 1 : c  with  c = max_norm / (sqrt(*sumsq) + 1e-6f)  : 1
+ *                                          (torch's clip_grad_norm_ coefficient min(1, c), a NaN staying a NaN as torch.clamp
+ *                                           keeps it; formed by every thread, the same in all)
+ *     g  = float32(grad[e]) * s            (no multiplication when sumsq is NULL)
+ *     p0 = master ? master[e] : float32(param[e])
+ *     p1 = p0 * decay
+ *     m' = m + w1 * (g - m)                m = exp_avg[e]
+ *     v' = v * b2 + w2 * (g * g)           v = exp_avg_sq[e]
+ *     d  = sqrt(v') / q + eps
+ *     p' = p1 - a * (m' / d)
+ *   exp_avg[e] = m', exp_avg_sq[e] = v', master[e] = p' when master is given, and param[e] = p' stored in the tensor's dtype
+ *   with ONE round-to-nearest-even (float32: as it is). The gradient is not written. A non-finite *sumsq propagates as torch's
+ *   default does (an infinite one gives s = 0 and NaN where the gradient is infinite, a NaN gives NaN everywhere); steps are
+ *   not skipped. No amsgrad, no maximize, no capturable mode.
+ * Consequences: every result depends on (the operands, the numbers) alone and *sumsq on the list alone: bitwise the same for
+ * every run, every alignment of the pointers and every split of the list over launches. Kernel shape (no part of the
+ * definition): one workgroup of 256 threads per (tensor, chunk); the list travels by value in the kernel's arguments,
+ * NOVA_ADAMW_BLOCK = 32 tensors with n > 0 per launch, so there is no device-side table, no host-to-device copy and no
+ * synchronisation, and no pointer is remembered between calls; 16-byte accesses where every pointer of the tensor is on 16
+ * bytes and the unit lies inside the tensor, element by element otherwise. Non-finite inputs are not checked (a training path).
+ * Errors of both, NOVA_ERR_ARG, in this order, before any device work: (1) count < 0; (2) a null `tensors` with count > 0;
+ * then per tensor in list order: (3) n outside 0 .. NOVA_ADAMW_MAX_N = 2^31 - 1; (4) an unknown dtype code; (5) for n > 0 a null
+ * param (step), grad, exp_avg (step), exp_avg_sq (step), in that order. Then, nova_adamw_sumsq with P > 0: (6) a null workspace,
+ * workspace_floats < P, a null sumsq, sumsq or norm inside the workspace's first P floats, norm on sumsq; nova_adamw_step: (6) max_norm <= 0 or NaN
+ * when sumsq is given. The texts are their own (no entry of the recorded error table).
+ * Added without a version bump (the number is pinned by the tests of earlier entries; a library without the new symbols
+ * fails to bind, loudly). */
+#define NOVA_ADAMW_CHUNK 8192
+#define NOVA_ADAMW_SUM_COLUMNS 256
+#define NOVA_ADAMW_BLOCK 32
+#define NOVA_ADAMW_MAX_N 2147483647
+typedef struct nova_adamw_tensor {
+  void* param;
+  const void* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  float* master;
+  long long n;
+  int dtype;
+  float decay, w1, b2, w2, q, a, eps;
+} nova_adamw_tensor;
+int nova_adamw_sumsq(const nova_adamw_tensor* tensors, int count, float* workspace, long long workspace_floats, float* sumsq,
+                     float* norm, void* stream);
+int nova_adamw_step(const nova_adamw_tensor* tensors, int count, const float* sumsq, float max_norm, void* stream);
+
 /* Nearest match with indices, and its backward: the primitive under the Chamfer-type training losses of the reference,
  * robust_chamfer_distance on distChamfer (train_newloss.py:316-349) and the edge-consistency term (train_newloss.py:449-457:
  * torch.cdist(subset1, subset2).min(dim=1), mean), which in PyTorch keep a [B, N, M] cdist matrix alive for the backward.

@@ -36,6 +36,11 @@ def autograd():
     return _module("autograd")
 
 
+def optim():
+    """The fused optimizer (nova_pointcloud_amd/optim.py): AdamW with the gradient clipping inside its HIP step."""
+    return _module("optim")
+
+
 def train_attention_supported(q, attn_mask):
     """bf16 device tensors [S, heads, L, 64 | 96] without a mask or with the block-causal frame mask: what the HIP attention
     forward + backward are built for."""

@@ -18,6 +18,7 @@ import time
 
 import torch
 
+from .. import _backend
 from . import engine_utils
 from .data_parallel import GradientReducer
 from .lr_scheduler import ConstantLR, CosineLR, MultiStepLR
@@ -56,6 +57,15 @@ def configure_model(model, config, noise_scheduler=None):
     return model
 
 
+def optimizer_class(target):
+    """The class an `optimizer.target` names by its last component: FusedAdamW is nova_pointcloud_amd.optim.FusedAdamW (AdamW
+    and the gradient clipping as one HIP pass), every other name a class of torch.optim."""
+    name = target.rsplit(".", 1)[-1]
+    if name == "FusedAdamW":
+        return _backend.optim().FusedAdamW
+    return getattr(torch.optim, name)
+
+
 class SmoothedValue(object):
     def __init__(self):
         self.total, self.count = 0.0, 0
@@ -71,7 +81,7 @@ class Trainer(object):
     """Schedule the iterative model training.
 
     config keys (the reference's YAML sections): training.{max_train_steps, gradient_accumulation_steps, seed, max_grad_norm},
-    optimizer.{target: AdamW|SGD|..., params}, lr_scheduler.{target, params}, experiment.{output_dir, log_every, save_every,
+    optimizer.{target: AdamW|SGD|...|FusedAdamW, params}, lr_scheduler.{target, params}, experiment.{output_dir, log_every, save_every,
     resume_iter}, model.{name, loss_repeat, gradient_checkpointing}, ema.params (optional), parallel.bucket_mb.
     """
 
@@ -96,7 +106,9 @@ class Trainer(object):
                 self.logger.warning("EMA configured but %s does not exist: averaging restarts from the resumed weights", ema_dir)
         groups = engine_utils.get_param_groups(self.model)
         opt = config.get("optimizer", {"target": "AdamW", "params": {"lr": 1e-4}})
-        self.optimizer = getattr(torch.optim, opt["target"].rsplit(".", 1)[-1])(groups, **opt.get("params", {}))
+        self.optimizer = optimizer_class(opt["target"])(groups, **opt.get("params", {}))
+        # FusedAdamW clips inside its step (one pass over the gradients, none written); every other optimizer is clipped by torch
+        self.fused_clip = opt["target"].rsplit(".", 1)[-1] == "FusedAdamW"
         sch = config.get("lr_scheduler", {"target": "ConstantLR", "params": {"lr_max": opt.get("params", {}).get("lr", 1e-4)}})
         self.scheduler = LR_SCHEDULERS[sch["target"].rsplit(".", 1)[-1]](**sch.get("params", {}))
         self.reducer = GradientReducer(list(self.model.parameters()), config.get("parallel", {}).get("bucket_mb", 256.0), process_group)
@@ -143,9 +155,12 @@ class Trainer(object):
             group["lr"] = stats["lr"] * group.get("lr_scale", 1.0)
         self.run_model(metrics, accum_steps)
         clip = self.config.get("training", {}).get("max_grad_norm", None)
-        if clip:
-            torch.nn.utils.clip_grad_norm_(self.model.parameters(), clip)
-        self.optimizer.step()
+        if self.fused_clip:
+            self.optimizer.step(max_grad_norm=clip or None)
+        else:
+            if clip:
+                torch.nn.utils.clip_grad_norm_(self.model.parameters(), clip)
+            self.optimizer.step()
         self.optimizer.zero_grad(set_to_none=True)
         self.scheduler.step()
         stats["time"] = time.time() - tic

@@ -59,6 +59,13 @@ class SamplerStep(ctypes.Structure):
     _fields_ = [(k, c_float) for k in ("guidance", "kx", "kv", "clip", "c0", "cx", "sigma", "extra_scale")] + [("extra_kind", c_int)]
 
 
+class AdamWTensor(ctypes.Structure):
+    """``nova_adamw_tensor`` (include/nova_hip.h): one tensor of the list a fused AdamW step walks."""
+
+    _fields_ = [(k, c_void_p) for k in ("param", "grad", "exp_avg", "exp_avg_sq", "master")] + [("n", ctypes.c_longlong), ("dtype", c_int)] + [
+        (k, c_float) for k in ("decay", "w1", "b2", "w2", "q", "a", "eps")]
+
+
 # name -> argtypes; every function returns int status. Must list EVERY symbol of nova_hip.h
 # (tests/test_abi.py checks the header against this table and against the built library).
 SIGNATURES = {
@@ -118,6 +125,8 @@ SIGNATURES = {
                               ctypes.c_ulonglong, ctypes.c_ulonglong, c_int, c_void_p],
     "nova_bias_dropout_add_bwd": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, ctypes.c_longlong, c_int, ctypes.c_longlong, ctypes.c_ulonglong, c_float,
                                   ctypes.c_ulonglong, ctypes.c_ulonglong, c_int, c_void_p],
+    "nova_adamw_sumsq": [ctypes.POINTER(AdamWTensor), c_int, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p],
+    "nova_adamw_step": [ctypes.POINTER(AdamWTensor), c_int, c_void_p, c_float, c_void_p],
     "nova_pointset_assignment": [c_void_p] * 5 + [c_int, c_int, c_float, c_float] + [c_int] * 3 + [c_void_p, c_void_p],
     "nova_pointset_assignment_rounds": [c_void_p, c_void_p, c_int, c_int, c_void_p],
     "nova_modulate_rows": [c_void_p] * 3 + [c_long, c_int, c_int, c_void_p],
